@@ -21,6 +21,16 @@ assembly.  Multi-GPU (one process per GPU):
 
 value = Hessian rows completed per second (whole job).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what that
+figure needs: set-up, W warm-up steps, K timed steps, one JSON line
+(`ms_per_step` = the timed region / K).  `--full` adds, outside the timed
+region, everything else the line can carry: the single-chain probe, the
+config-2 gradient block, the CPU baselines (the oracle on host threads) with
+their GPU comparisons and, at N=1, the config-4 / config-5 slice blocks (child
+processes run before the config-1 measurement).  `--dump-outputs DIR` writes
+what the last timed step returned (Hessian, gradient, divT, F) as .npy files;
+all inputs are seeded, so two builds can be compared output for output.
+
 Other workloads (--workload; one JSON line each, not the driver's default):
   gradient   config 2: getAnalyticGradient with BFGS=true (psi and xi chains
              concurrently, divT, F; src/OptimalControl.cpp:204-249) at config 1,
@@ -59,7 +69,17 @@ def parse_args(argv=None):
                     help="ranks (one process per GPU); without an outer launcher bench.py spawns them itself")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can carry: the single-chain "
+                         "probe, the config-2 gradient block, the CPU baselines with their GPU comparisons and, for "
+                         "config 1 at N=1, the config-4 / config-5 slice blocks (child processes).  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller (the Hessian, "
+                         "the gradient, divT, F) as DIR/<name>.npy, float64 (complex values as re, im pairs); "
+                         "rank 0 writes.  The inputs are seeded: two runs with the same arguments compare output "
+                         "for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-threads", type=int, default=0, help="largest CPU-baseline thread count (0: all available)")
     ap.add_argument("--mode", choices=["weak", "strong"], default=None,
                     help="weak: every rank its own getHessian; strong: one getHessian's rows over the ranks "
@@ -92,14 +112,45 @@ def parse_args(argv=None):
                          "block, no config-4 / config-5 slice blocks, no CPU baseline): the command rocprofv3 "
                          "profiles, so every dispatch of a kernel belongs to the population the roofline divides by")
     ap.add_argument("--no-slices", action="store_true",
-                    help="config 1 at N=1: skip the config-4 / config-5 slice blocks (child processes run before "
-                         "the config-1 line)")
+                    help="with --full, config 1 at N=1: skip the config-4 / config-5 slice blocks (child processes "
+                         "run before the config-1 line)")
     ap.add_argument("--c4-cpu-nt", type=int, default=5,
                     help="time points of the measured oracle getHessian in the c4rows CPU baseline (0: skip)")
     ap.add_argument("--multi-info", action="store_true",
-                    help="after the timed region also time 8 Hessians / 64 gradients per call (ocg_*_multi; "
+                    help="with --full: after the timed region also time 8 Hessians / 64 gradients per call (ocg_*_multi; "
                          "their k_pipeline launches would enter a rocprofv3 summary of the command)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=20261019):
+    """--dump-outputs: every array of `arrays` (name -> array) as
+    DIR/<name>.npy in float64, complex values as (..., 2) re / im pairs.  Beyond
+    DUMP_LIMIT_BYTES in all, each array is cut to its share of the limit: a
+    fixed sample of its flattened entries (indices drawn once from `seed`,
+    sorted), the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a, dtype=np.complex128).view(np.float64).reshape(a.shape + (2,))
+        out[name] = np.ascontiguousarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(seed)
+        for name in sorted(out):
+            a = out[name].reshape(-1)
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES - 4096 * len(out)) / total))
+            if keep < a.size:
+                out[name] = a[np.sort(rng.choice(a.size, size=keep, replace=False))]
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def free_port():
@@ -178,8 +229,8 @@ def main(argv=None):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, argv)
     blocks = None
-    if (args.workload == "hessian" and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1
-            and not args.profiled and not args.no_slices and args.multi == 1 and args.controls == 1):
+    if (args.full and args.workload == "hessian" and args.gpus == 1
+            and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.profiled and not args.no_slices and args.multi == 1 and args.controls == 1):
         # before this process touches the GPU: the children start from a process
         # that never made a HIP call (no exec of a GPU process, no fork of one)
         blocks = slice_blocks(args)
@@ -194,7 +245,7 @@ SLICE_TIMEOUT_S = 420
 
 
 def slice_blocks(args):
-    """Configs 4 and 5 (BASELINE configs[3], configs[4]) in the default N=1 line:
+    """Configs 4 and 5 (BASELINE configs[3], configs[4]) in the N=1 line of a --full run:
     each runs as `bench.py --workload c4rows|c5rows` in a fresh child interpreter
     (its own HIP context; nothing of this process is inherited but the
     environment), one after the other and before the config-1 measurement, so
@@ -204,7 +255,7 @@ def slice_blocks(args):
     timed)."""
     import subprocess
     me = os.path.abspath(__file__)
-    common = ["--gpus", "1", "--profile-tag", args.profile_tag, "--cpu-threads", str(args.cpu_threads)]
+    common = ["--gpus", "1", "--full", "--profile-tag", args.profile_tag, "--cpu-threads", str(args.cpu_threads)]
     if args.no_cpu_baseline:
         common.append("--no-cpu-baseline")
     jobs = [("config4_slice", ["--workload", "c4rows", "--c4-nt", "33", "--steps", "2", "--warmup", "1",
@@ -290,15 +341,18 @@ def run(args, blocks=None):
         if KM > 1:   # all KM controls in one pipeline launch (ocg_hessian_multi)
             Hm, dm, Fm = eng.hessian_multi(U_multi, rows)
             H, divT, F = Hm[0], dm[0], Fm[0]
+            got = {"hessian": Hm, "divT": dm, "F": Fm}
         else:
             H, divT, F = eng.hessian(u, rows)
+            got = {"hessian": H, "divT": divT, "F": np.array([F])}
         for f in futs:
             f.result()
         g = dt * (divT * F * 1j).real            # calcFidelityGrad (gamma = 0)
         if world > 1 and strong:
             Hdev.copy_(torch.from_numpy(H))
             dist.reduce(Hdev, dst=0)             # RCCL sum of disjoint row entries
-        return g, H
+        got["gradient"] = g
+        return got
 
     for _ in range(args.warmup):
         one_step()
@@ -308,7 +362,7 @@ def run(args, blocks=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -318,6 +372,10 @@ def run(args, blocks=None):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        if world > 1 and strong:
+            last["hessian"] = Hdev.cpu().numpy()   # the summed Hessian, as rank 0's caller holds it
+        dump_outputs(args.dump_outputs, last)
 
     K = K * KM   # control vectors per GPU per step (contexts x controls per launch)
     rows_total = (Nt - 2) * args.steps * (1 if strong else world) * K
@@ -326,14 +384,15 @@ def run(args, blocks=None):
     st_ovl = eng.stats(6)        # k_row_overlaps
     st_div = eng.stats(1)        # divT / F overlaps
     t_tr = None
-    if not args.profiled:        # a profiled command holds only the timed population
+    extras = args.full and not args.profiled   # a profiled command holds only the timed population
+    if extras:
         t_tr = time.perf_counter()
         eng.propagate(u, 3)      # one bare psi || xi trajectory (outside the timed region): single-chain step rate
         t_tr = time.perf_counter() - t_tr
     # throughput with several control vectors per call (IPOPT trial points, FD probes,
     # multi-start), outside the timed region: reported beside `value`, never as it
     multi_info = None
-    if args.multi_info and K * KM == 1 and not strong:
+    if args.full and args.multi_info and K * KM == 1 and not strong:
         Um = np.random.default_rng(CFG["seed"] + 77 + rank).uniform(2.0, 10.0, (8, Nt))
         eng.hessian_multi(Um[:2], rows)              # warm the multi path's buffers
         torch.cuda.synchronize()
@@ -392,11 +451,11 @@ def run(args, blocks=None):
         result["env"] = run_env()
         # config 2 (BASELINE configs[1]) after the timed region, as main/TestRuntimes.cpp:55-63
         # times getAnalyticGradient before getHessian
-        if not args.profiled:
+        if extras:
             result["config2_gradient"] = config2_gradient(eng, u, Nt, dt, args.profile_tag,
                                                           cpu=(world == 1 and not args.no_cpu_baseline),
                                                           ini=ini, tgt=tgt)
-        if world == 1 and not args.no_cpu_baseline and not args.profiled:
+        if world == 1 and not args.no_cpu_baseline and extras:
             result["cpu_baseline"] = cpu_baseline(ini, tgt, u, args.cpu_threads)
         if blocks:   # configs 4 and 5, measured in child processes before this line's timed region
             result.update(blocks)
@@ -557,7 +616,7 @@ def bench_gradient(args, eng, u, Nt, dt, world, rank, dist, cdev, U_multi):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one()
+        g = one()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -566,6 +625,8 @@ def bench_gradient(args, eng, u, Nt, dt, world, rank, dist, cdev, U_multi):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gradient": g})
     st_traj, st_ov = eng.stats(0), eng.stats(1)
     if rank == 0:
         launch_ms = st_traj["ms"] / max(1, st_traj["launches"])
@@ -730,7 +791,7 @@ def bench_c4(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.warmup, nsteps_all):
-        one(s)
+        last = one(s)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -740,11 +801,13 @@ def bench_c4(args):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gradient" if grad else "hessian": last})
     gm = eng.stats(7)   # k_gemm: the MFMA-FP64 contraction kernel
     # one bare psi chain (ocg_propagate(u, 1)) outside the timed region: the single-chain step rate
     t_sc = None
     paths = eng.path_stats()
-    if not args.profiled and not (grad and c5) and not paths["ckpt_runs"]:
+    if args.full and not args.profiled and not (grad and c5) and not paths["ckpt_runs"]:
         # a profiled command holds only the timed population; config 5's full-horizon trajectories
         # do not fit the device (the gradient meets in the middle, the getHessian checkpoints)
         t_sc = time.perf_counter()
@@ -820,7 +883,7 @@ def bench_c4(args):
                 "whole_source": "profiles/r06_bench_c4full.json (round 6 code: one GPU, the two-phase path; "
                                 "rounds 4-5: 359-366 s, profiles/r04_bench_c4full_prio.json)"}
         res["env"] = run_env()
-        if world == 1 and not args.no_cpu_baseline and not grad and not args.profiled:
+        if args.full and world == 1 and not args.no_cpu_baseline and not grad and not args.profiled:
             res["cpu_baseline"] = (cpu_baseline_c5(ini, Nt, args.cpu_threads) if c5 else
                                    cpu_baseline_c4(ini, tgt, Nt, args.cpu_threads, args.c4_cpu_nt))
         print(json.dumps(res), flush=True)

@@ -76,10 +76,11 @@ def test_main_spawns_without_launcher(monkeypatch):
     assert bench.main(["--gpus", "4"]) == 0
     assert bench.main(["--gpus", "1"]) == 0
     monkeypatch.delenv("WORLD_SIZE")
-    assert bench.main(["--gpus", "1"]) == 0                    # N=1 default: the slice blocks first
-    assert bench.main(["--gpus", "1", "--no-slices"]) == 0
-    assert bench.main(["--gpus", "1", "--profiled"]) == 0
-    assert calls == [("spawn", 4), ("run", 4, None), ("run", 1, None),
+    assert bench.main(["--gpus", "1"]) == 0                    # a plain run: the headline figure only
+    assert bench.main(["--gpus", "1", "--full"]) == 0          # N=1 --full: the slice blocks first
+    assert bench.main(["--gpus", "1", "--full", "--no-slices"]) == 0
+    assert bench.main(["--gpus", "1", "--full", "--profiled"]) == 0
+    assert calls == [("spawn", 4), ("run", 4, None), ("run", 1, None), ("run", 1, None),
                      ("run", 1, {"config4_slice": {}, "config5_slice": {}}), ("run", 1, None), ("run", 1, None)]
 
 
@@ -104,3 +105,24 @@ def test_slice_blocks_children(monkeypatch):
     assert [c[0][3:5] for c in seen] == [["--workload", "c4rows"], ["--workload", "c5rows"], ["--workload", "c4rows"]]
     assert "--row-stride" in seen[2][0] and "801" in seen[2][0]
     assert all("RANK" not in env for _, env in seen)
+    assert all("--full" in cmd for cmd, _ in seen)             # the children carry their CPU baselines
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files, complex values as re / im pairs; beyond the
+    size limit a sample of each array that is the same from run to run"""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    H, d = rng.normal(size=(7, 7)), rng.normal(size=7) + 1j * rng.normal(size=7)
+    bench.dump_outputs(str(tmp_path / "a"), {"hessian": H, "divT": d})
+    assert sorted(os.listdir(tmp_path / "a")) == ["divT.npy", "hessian.npy"]
+    Hd, dd = np.load(tmp_path / "a" / "hessian.npy"), np.load(tmp_path / "a" / "divT.npy")
+    assert Hd.dtype == np.float64 and np.array_equal(Hd, H)
+    assert dd.dtype == np.float64 and dd.shape == (7, 2) and np.array_equal(dd[:, 0] + 1j * dd[:, 1], d)
+    big = rng.normal(size=4000)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16384)
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), {"big": big, "hessian": H})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert np.array_equal(b, c) and 0 < b.size < big.size and np.isin(b, big).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 16384
