@@ -72,7 +72,7 @@ int ocg_destroy(ocg_ctx* ctx);
 /* last error message of ctx (or of the last failed ocg_create when ctx == NULL) */
 const char* ocg_last_error(const ocg_ctx* ctx);
 /* writes sizeof(ocg_info) bytes of the header the library was built with
- * (ABI version 3: fast_chain is the last field); callers built against
+ * (since ABI version 3: fast_chain is the last field); callers built against
  * another version use ocg_get_info_sz */
 int ocg_get_info(const ocg_ctx* ctx, ocg_info* info);
 /* as ocg_get_info, writing at most info_size bytes (the caller's sizeof(ocg_info)) */
@@ -80,8 +80,9 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
 /* ABI version of the library (OCG_ABI_VERSION of the header it was built with).
  * Changelog: 2 ocg_info.fast_chain (round 5), OCG_ENOMEM returned by
  * ocg_hessian when OCG_HBM_PIPE=1 forces a pipeline that cannot allocate;
- * 3 ocg_get_info_sz, ocg_get_path_stats, ocg_abi_version (round 6). */
-#define OCG_ABI_VERSION 3
+ * 3 ocg_get_info_sz, ocg_get_path_stats, ocg_abi_version (round 6);
+ * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9. */
+#define OCG_ABI_VERSION 4
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
 int ocg_set_tstep(ocg_ctx* ctx, double tstep);
@@ -211,6 +212,33 @@ int ocg_gradient_multi(ocg_ctx* ctx, int K, const double* u, int N, double* divT
  * ocg_steps returns are in the reference's gauge. */
 int ocg_get_state(ocg_ctx* ctx, int which, int t, int* dims, double* data, size_t cap, size_t* nelem);
 
+/* Observables of the device-resident trajectory states, evaluated where the
+ * states are (the drivers' loops over OC.getPsit(): <N_i>, <N_i^2>, bond
+ * dimensions, a+a / nn correlation rows).  which: 0 psi_t, 1 xi_t, 2 xiHlist,
+ * existing as for ocg_get_state (OCG_ESTATE otherwise).  ts[0..nt): state
+ * indices in 0..N-1, any order, repeats allowed; ts == NULL: 0..nt-1.
+ * rows[0..nrows): start sites in 1..L (nrows == 0: no correlations).
+ * Outputs (NULL: skipped, and its work not done):
+ *   norm2[nt]                 <s|s>
+ *   occ[nt][L][p]             raw occupation distribution (not divided by
+ *                             norm2): <N> = sum n occ, <NN> = sum n^2 occ, ...
+ *   bond[nt][L+1]             bond dimensions
+ *   corr_ada[nt][nrows][L][2] <a+_i a_j> for j >= i, interleaved (re, im)
+ *   corr_nn[nt][nrows][L]     <n_i n_j> for j >= i
+ * Entries j < i of a row are 0 (rho_ji = conj(rho_ij)); the j = i entries are
+ * real (sum n occ, sum n^2 occ).  Gauge-free (environments from both ends), so
+ * intermediate, unnormalised and truncated states are fine.  The states are
+ * processed in chunks whose workspace fits half the free device memory
+ * (OCG_ENOMEM if not even one state's does); a state's results are bit-identical
+ * whatever else is requested with it.  Reads the trajectories only. */
+int ocg_observe(ocg_ctx* ctx, int which, const int* ts, int nt, const int* rows, int nrows, double* norm2,
+                double* occ, int* bond, double* corr_ada, double* corr_nn);
+/* The same for n caller-supplied host states (state i = dims + i*(L+1)*(Q+1),
+ * data[i]; any gauge or norm), staged in the scratch slots behind the
+ * trajectories as ocg_step_batch does, in batches. */
+int ocg_observe_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, const int* rows, int nrows,
+                       double* norm2, double* occ, int* bond, double* corr_ada, double* corr_nn);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -244,7 +272,10 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * retries after a pipeline that failed with OCG_ENOMEM; never with
  * OCG_HBM_PIPE=1, which makes any pipeline failure the call's status),
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
- * segment length of the last one).  Sums since the last reset. */
+ * segment length of the last one), 9 the observable kernels of ocg_observe /
+ * ocg_observe_states (HIP-event time of their chunks, kernel launches, and the
+ * algorithmic bytes and flops of the host-built task lists).  Sums since the
+ * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,
                      double* alg_flops, long* sweep_steps);
 int ocg_reset_stats(ocg_ctx* ctx);

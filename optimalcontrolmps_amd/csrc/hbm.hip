@@ -36,6 +36,7 @@
 
 #include "hbm.hpp"
 #include "hbm_device.hpp"
+#include "observe.hpp"
 
 namespace hbm {
 
@@ -2280,9 +2281,10 @@ struct hbm_engine {
   int psi_base() const { return 4; }
   int xi_base() const { return 4 + N; }
   int xih_base() const { return 4 + 2 * N; }
-  double ms[8] = {0};
-  long launches[8] = {0};
-  long steps[8] = {0};
+  double ms[10] = {0};
+  long launches[10] = {0};
+  long steps[10] = {0};
+  obs::Traffic obs_tr;  // kind 9: the observable kernels' algorithmic traffic and launches
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
@@ -3154,6 +3156,192 @@ int hbm_get_state(hbm_engine* h, int which, int t, int* dims, double* data, size
   });
 }
 
+// ---------------------------------------------------------------- observables
+namespace {
+// observe.hpp's task lists on this engine: the contractions on k_gemm, the
+// workspace from the arenas (recycled at the chunk's sync)
+struct ObsBackend {
+  hbm::Engine& E;
+  double* alloc(size_t n) { return reinterpret_cast<double*>(E.walloc<hbm::z>(n)); }
+  const double* one() {
+    hbm::z* o = E.walloc<hbm::z>(1);
+    std::vector<hbm::CTask> ct{hbm::Engine::ctask(nullptr, o, 1, 1, 0, 1, 8)};  // fill with f = 1
+    E.copy(ct);
+    return reinterpret_cast<const double*>(o);
+  }
+  void gemm(std::vector<obs::Task>& t, std::vector<obs::Seg>& s) {
+    std::vector<hbm::GTask> gt;
+    std::vector<hbm::GSeg> gs;
+    gt.reserve(t.size());
+    gs.reserve(s.size());
+    for (auto& x : t)
+      gt.push_back(hbm::Engine::gtask(reinterpret_cast<hbm::z*>(x.C), x.ldc, x.m, x.n, x.seg0, x.nseg));
+    for (auto& x : s)
+      gs.push_back(hbm::Engine::gseg(reinterpret_cast<const hbm::z*>(x.A), x.lda, reinterpret_cast<const hbm::z*>(x.B),
+                                     x.ldb, x.k, x.ops, x.alpha));
+    E.gemm(gt, gs);
+    t.clear();
+    s.clear();
+  }
+  void close(std::vector<obs::CTask>& t, std::vector<obs::Pair>& p, double* out) {
+    if (!t.empty()) {
+      const obs::CTask* dt = E.upload(t);
+      const obs::Pair* dp = E.upload(p);
+      hipLaunchKernelGGL(obs::k_obs_close, dim3(unsigned(t.size())), dim3(obs::kCloseNT), 0, E.st, dt, dp, out);
+      HCK(hipGetLastError());
+    }
+    t.clear();
+    p.clear();
+  }
+};
+
+obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
+  obs::StateDesc d;
+  d.dims = s.dims.v;
+  d.blk.assign(size_t(E.L + 1) * E.Q1 * E.p, obs::Blk{});
+  for (int k = 1; k <= E.L; ++k) {
+    const hbm::SiteLayout sl = hbm::site_layout(s.dims, k, E.p);
+    for (int q = 0; q < E.Q1; ++q)
+      for (int n = 0; n < E.p && q + n < E.Q1; ++n) {
+        int ld = 0;
+        const long o = sl.blk(q, n, E.p, s.dims, k, &ld);
+        if (o < 0 || ld == 0) continue;
+        d.blk[(size_t(k) * E.Q1 + q) * E.p + n] =
+            obs::Blk{reinterpret_cast<const double*>(s.data + s.off[k] + o), s.dims(k - 1, q), ld};
+      }
+  }
+  return d;
+}
+
+// the observables of state slots[i] into entry out0 + i of the outputs, in
+// chunks whose workspace fits half the free HBM
+void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
+                   double* occ_buf) {
+  hbm::Engine& E = *h->E;
+  const int L = E.L, nst = int(slots.size());
+  std::vector<obs::StateDesc> desc(nst);
+  for (int i = 0; i < nst; ++i) {
+    desc[i] = obs_desc(E, E.states[slots[i]]);
+    if (bond)
+      for (int b = 0; b <= L; ++b) bond[(out0 + i) * (L + 1) + b] = E.states[slots[i]].dims.bond(b);
+  }
+  const obs::Want want = obs::want_of(o);
+  if (!want.norm && !want.env()) return;
+  const std::vector<int> rows(o.rows, o.rows + o.nrows);
+  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want);
+  const size_t budget = obs::chunk_budget();
+  for (int i0 = 0; i0 < nst;) {
+    int i1 = i0;
+    size_t sum = 0;
+    while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
+    std::vector<const obs::StateDesc*> S;
+    std::vector<size_t> os;
+    for (int i = i0; i < i1; ++i) {
+      S.push_back(&desc[i]);
+      os.push_back(out0 + i);
+    }
+    ObsBackend be{E};
+    std::vector<obs::Dest> dests;
+    Timer t(h, 9);
+    const double* d_out = obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr);
+    std::vector<double> res(2 * std::max<size_t>(dests.size(), 1));
+    if (!dests.empty())
+      HCK(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost, E.st));
+    t.stop();
+    E.sync();
+    obs::scatter(dests, res.data(), o, occ_buf);
+    if (o.nrows > 0 && (o.ada || o.nn))
+      for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
+    i0 = i1;
+  }
+}
+
+// caller-supplied states staged per batch: a quarter of the free HBM, 64 at the most
+int hbm_batch_states(hbm_engine* h) {
+  size_t fr = 0, tot = 0;
+  (void)hipMemGetInfo(&fr, &tot);
+  const double per = 16.0 * double(std::max<long>(h->E->state_cap, 1));
+  return int(std::max(1.0, std::min(64.0, 0.25 * double(fr) / per)));
+}
+
+void observe_check_rows(const hbm::Engine& E, const int* rows, int nrows) {
+  if (nrows < 0 || (nrows > 0 && !rows)) throw hbm::Error(1, "bad rows");
+  for (int i = 0; i < nrows; ++i)
+    if (rows[i] < 1 || rows[i] > E.L) throw hbm::Error(1, "row (start site) out of 1..L");
+}
+}  // namespace
+
+int hbm_observe(hbm_engine* h, int which, const int* ts, int nt, const int* rows, int nrows, double* norm2,
+                double* occ, int* bond, double* ada, double* nn) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
+    const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
+    if (!ok) throw hbm::Error(4, "requested trajectory not available");
+    observe_check_rows(E, rows, nrows);
+    const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
+    std::vector<int> slots(nt);
+    for (int i = 0; i < nt; ++i) {
+      const int t = ts ? ts[i] : i;
+      if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
+      slots[i] = base + t;
+    }
+    if (nt == 0) return;
+    obs::Outputs o{norm2, occ, ada, nn, E.L, E.p, nrows, rows};
+    std::vector<double> tmp;
+    double* occ_buf = occ;
+    if (!occ && obs::want_of(o).occ) {
+      tmp.assign(size_t(nt) * E.L * E.p, 0.0);
+      occ_buf = tmp.data();
+    }
+    if (ada) std::fill(ada, ada + 2 * size_t(nt) * nrows * E.L, 0.0);
+    if (nn) std::fill(nn, nn + size_t(nt) * nrows * E.L, 0.0);
+    observe_slots(h, slots, 0, o, bond, occ_buf);
+  });
+}
+
+int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* const* data, const int* rows, int nrows,
+                       double* norm2, double* occ, int* bond, double* ada, double* nn) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
+    observe_check_rows(E, rows, nrows);
+    if (n == 0) return;
+    const int nsq = (E.L + 1) * E.Q1;
+    for (int i = 0; i < n; ++i) {
+      const int* d = dims + size_t(i) * nsq;
+      for (int j = 0; j < nsq; ++j)
+        if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
+      for (int q = 0; q < E.Q1; ++q)
+        if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
+          throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
+      E.set_caps(widest_of(E, d));
+    }
+    obs::Outputs o{norm2, occ, ada, nn, E.L, E.p, nrows, rows};
+    std::vector<double> tmp;
+    double* occ_buf = occ;
+    if (!occ && obs::want_of(o).occ) {
+      tmp.assign(size_t(n) * E.L * E.p, 0.0);
+      occ_buf = tmp.data();
+    }
+    if (ada) std::fill(ada, ada + 2 * size_t(n) * nrows * E.L, 0.0);
+    if (nn) std::fill(nn, nn + size_t(n) * nrows * E.L, 0.0);
+    // staged in the scratch slots behind the trajectories, a batch at a time
+    const int B = std::min(hbm_batch_states(h), n);
+    const int sb = h->xih_base() + h->N;
+    E.reserve_states(size_t(sb + B));
+    for (int i0 = 0; i0 < n; i0 += B) {
+      const int nb = std::min(B, n - i0);
+      std::vector<int> slots(nb);
+      for (int i = 0; i < nb; ++i) {
+        slots[i] = sb + i;
+        E.upload_state(E.states[sb + i], dims + size_t(i0 + i) * nsq, data[i0 + i]);
+      }
+      observe_slots(h, slots, size_t(i0), o, bond, occ_buf);
+    }
+  });
+}
+
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps) {
   if (kind == 7) {  // the GEMM (MFMA contraction) kernel: HIP-event time, algorithmic flops / bytes
     (void)guard(h, [&] { h->E->sync(); });
@@ -3161,6 +3349,14 @@ int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes
     if (launches) *launches = h->E->gemm_launches;
     if (bytes) *bytes = h->E->gemm_bytes;
     if (flops) *flops = h->E->gemm_flops;
+    if (steps) *steps = 0;
+    return 0;
+  }
+  if (kind == 9) {  // the observable kernels (observe.hpp)
+    if (ms) *ms = h->ms[9];
+    if (launches) *launches = h->obs_tr.launches;
+    if (bytes) *bytes = h->obs_tr.bytes;
+    if (flops) *flops = h->obs_tr.flops;
     if (steps) *steps = 0;
     return 0;
   }
@@ -3192,7 +3388,8 @@ int hbm_coop_stats(hbm_engine* h, long* launches, long* groups, long* fallbacks)
   return rc;
 }
 void hbm_reset_stats(hbm_engine* h) {
-  for (int k = 0; k < 8; ++k) { h->ms[k] = 0; h->launches[k] = 0; h->steps[k] = 0; }
+  for (int k = 0; k < 10; ++k) { h->ms[k] = 0; h->launches[k] = 0; h->steps[k] = 0; }
+  h->obs_tr = obs::Traffic{};
   (void)guard(h, [&] { h->E->sync(); });
   h->E->gemm_ms = h->E->gemm_flops = h->E->gemm_bytes = 0;
   h->E->gemm_launches = 0;

@@ -59,8 +59,13 @@ double hbm_traj_bytes(const hbm_engine* h, int N);
 // slots and 2 K chains (0 when the engine already holds them)
 double hbm_gradient_multi_bytes(const hbm_engine* h, int K, int N);
 int hbm_get_state(hbm_engine* h, int which, int t, int* dims, double* data, size_t cap, size_t* nelem);
+// ocg_observe / ocg_observe_states (observe.hpp's task lists on k_gemm + the close kernel)
+int hbm_observe(hbm_engine* h, int which, const int* ts, int nt, const int* rows, int nrows, double* norm2,
+                double* occ, int* bond, double* ada, double* nn);
+int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* const* data, const int* rows, int nrows,
+                       double* norm2, double* occ, int* bond, double* ada, double* nn);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM
-// kernel (k_gemm) with its algorithmic bytes and flops
+// kernel (k_gemm) with its algorithmic bytes and flops; 9: the observable kernels
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps);
 // multi-CU eigenvalue launches, blocks reduced by groups, groups re-run on one CU
 // (the context engine and the pipelined getHessian's workers, since creation)

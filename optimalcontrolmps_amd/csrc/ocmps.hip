@@ -23,6 +23,7 @@
 #include "engine_device.hpp"
 #include "params.hpp"
 #include "fast_plan.hpp"
+#include "observe.hpp"
 
 using ocg::Chain;
 using ocg::zc;
@@ -280,7 +281,10 @@ struct ocg_ctx {
   int N = 0;
   std::vector<double> u_psi, u_xi;  // controls of the device psi_t / xi_t (empty: none)
   bool have_states = false, have_psi = false, have_xi = false, have_xih = false;
-  KStat kst[8];
+  KStat kst[10];
+  char* d_obs = nullptr;  // observable workspace kept between calls (up to kObsKeepBytes)
+  size_t obs_cap = 0;
+  obs::Traffic obs_tr;  // kind 9: the observable kernels' algorithmic traffic and launches
   // slot map
   int slot_init() const { return 0; }
   int slot_target() const { return 1; }
@@ -775,6 +779,7 @@ int ocg_destroy(ocg_ctx* c) {
   if (c->pool.dims) (void)hipFree(c->pool.dims);
   if (c->pool.data) (void)hipFree(c->pool.data);
   if (c->d_stats) (void)hipFree(c->d_stats);
+  if (c->d_obs) (void)hipFree(c->d_obs);
   if (c->rs.dims) (void)hipFree(c->rs.dims);
   if (c->rs.data) (void)hipFree(c->rs.data);
   if (c->d_flags) (void)hipFree(c->d_flags);
@@ -1791,9 +1796,190 @@ int ocg_get_state(ocg_ctx* c, int which, int t, int* dims, double* data, size_t 
   return download_mps(c, base + t, dims, data, cap, nelem);
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------ observables
+// The LDS engine's side of ocg_observe: block descriptors of pool slots (a
+// slot holds the compact format, site k at site_base[k]) and observe.hpp's
+// driver on a workspace sized by its dry run, in chunks of at most half the
+// free device memory.  Reads the slots only.
+static constexpr size_t kObsKeepBytes = size_t(256) << 20;
+static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
+                         double* occ_buf) {
+  const OcgParams& P = c->P;
+  const int nst = int(slots.size());
+  std::vector<obs::StateDesc> desc(nst);
+  // the dims of the slot range in one copy (a trajectory's slots are neighbours)
+  const int s0 = *std::min_element(slots.begin(), slots.end()), s1 = *std::max_element(slots.begin(), slots.end());
+  std::vector<int> hd(size_t(s1 - s0 + 1) * P.nsq);
+  HIPCHK(c, hipMemcpyAsync(hd.data(), SLOT_D(c->pool, P, s0), sizeof(int) * hd.size(), hipMemcpyDeviceToHost,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < nst; ++i)
+    desc[i].dims.assign(hd.begin() + size_t(slots[i] - s0) * P.nsq, hd.begin() + size_t(slots[i] - s0 + 1) * P.nsq);
+  for (int i = 0; i < nst; ++i) {
+    const int* d = desc[i].dims.data();
+    desc[i].blk.assign(size_t(P.L + 1) * P.Q1 * P.p, obs::Blk{});
+    for (int k = 1; k <= P.L; ++k) {
+      size_t off = 0;
+      for (int q = 0; q < P.Q1; ++q)
+        for (int n = 0; n < P.p && q + n <= P.Q; ++n) {
+          const int r = d[(k - 1) * P.Q1 + q], cc = d[k * P.Q1 + q + n];
+          if (r <= 0 || cc <= 0) continue;
+          desc[i].blk[(size_t(k) * P.Q1 + q) * P.p + n] = obs::Blk{
+              reinterpret_cast<const double*>(SLOT_X(c->pool, P, slots[i]) + P.site_base[k] + off), r, cc};
+          off += size_t(r) * cc;
+        }
+      if (off > size_t(P.site_cap[k])) return fail(c, OCG_ESTATE, "internal: slot dims exceed the site capacity");
+    }
+    if (bond)
+      for (int b = 0; b <= P.L; ++b) {
+        int sum = 0;
+        for (int q = 0; q < P.Q1; ++q) sum += d[b * P.Q1 + q];
+        bond[(out0 + i) * (P.L + 1) + b] = sum;
+      }
+  }
+  const obs::Want want = obs::want_of(o);
+  if (!want.norm && !want.env()) return 0;
+  const std::vector<int> rows(o.rows, o.rows + o.nrows);
+  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want);
+  const size_t budget = obs::chunk_budget();
+  for (int i0 = 0; i0 < nst;) {
+    int i1 = i0;
+    size_t sum = 0;
+    while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
+    std::vector<const obs::StateDesc*> S;
+    std::vector<size_t> os;
+    for (int i = i0; i < i1; ++i) {
+      S.push_back(&desc[i]);
+      os.push_back(out0 + i);
+    }
+    obs::RawBackend be;
+    // small workspaces stay with the context (an allocation and a free per call cost more than the kernels)
+    const bool keep = sum <= kObsKeepBytes;
+    if (keep && sum <= c->obs_cap) {
+      be.base = c->d_obs;
+    } else {
+      if (keep && c->d_obs) {
+        (void)hipFree(c->d_obs);
+        c->d_obs = nullptr;
+        c->obs_cap = 0;
+      }
+      if (hipMalloc((void**)&be.base, sum) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, OCG_ENOMEM,
+                    "observables: the workspace of one chunk (" + std::to_string(sum) + " B) does not fit");
+      }
+      if (keep) {
+        c->d_obs = be.base;
+        c->obs_cap = sum;
+      }
+    }
+    be.cap = sum;
+    be.st = c->stream;
+    std::vector<obs::Dest> dests;
+    obs::Traffic tr;
+    int rc = begin_kernel(c);
+    std::vector<double> res;
+    if (!rc) {
+      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr);
+      res.resize(2 * std::max<size_t>(dests.size(), 1));
+      if (be.ok() && !dests.empty())
+        be.note(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost,
+                               c->stream));
+      rc = end_kernel(c, 9);  // synchronises the stream
+      if (!rc && !be.ok())
+        rc = fail(c, be.overflow ? OCG_ENOMEM : OCG_EHIP,
+                  be.overflow ? std::string("observables: workspace overflow")
+                              : std::string("observables: ") + hipGetErrorString(be.err));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    if (!keep) (void)hipFree(be.base);
+    if (rc) return rc;
+    c->obs_tr.bytes += tr.bytes;
+    c->obs_tr.flops += tr.flops;
+    c->obs_tr.launches += tr.launches;
+    obs::scatter(dests, res.data(), o, occ_buf);
+    if (o.nrows > 0 && (o.ada || o.nn))
+      for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
+    i0 = i1;
+  }
+  return 0;
+}
+
+static int observe_check_rows(ocg_ctx* c, const int* rows, int nrows) {
+  if (nrows < 0 || (nrows > 0 && !rows)) return fail(c, OCG_EINVAL, "bad rows");
+  for (int i = 0; i < nrows; ++i)
+    if (rows[i] < 1 || rows[i] > c->P.L) return fail(c, OCG_EINVAL, "row (start site) out of 1..L");
+  return 0;
+}
+
+// zero the row outputs (entries j < i stay 0) and pick the occupation buffer
+static double* observe_prepare(const obs::Outputs& o, size_t n, std::vector<double>& tmp) {
+  if (o.ada) std::fill(o.ada, o.ada + 2 * n * o.nrows * o.L, 0.0);
+  if (o.nn) std::fill(o.nn, o.nn + n * o.nrows * o.L, 0.0);
+  if (o.occ || !obs::want_of(o).occ) return o.occ;
+  tmp.assign(n * o.L * o.p, 0.0);
+  return tmp.data();
+}
+
+extern "C" {
+
+int ocg_observe(ocg_ctx* c, int which, const int* ts, int nt, const int* rows, int nrows, double* norm2, double* occ,
+                int* bond, double* corr_ada, double* corr_nn) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm)
+    return hb(c, hbm_observe(c->hbm, which, ts, nt, rows, nrows, norm2, occ, bond, corr_ada, corr_nn));
+  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
+  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
+  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
+  if (int rc = observe_check_rows(c, rows, nrows)) return rc;
+  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
+  std::vector<int> slots(nt);
+  for (int i = 0; i < nt; ++i) {
+    const int t = ts ? ts[i] : i;
+    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
+    slots[i] = base + t;
+  }
+  if (nt == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const obs::Outputs o{norm2, occ, corr_ada, corr_nn, c->P.L, c->P.p, nrows, rows};
+  std::vector<double> tmp;
+  double* occ_buf = observe_prepare(o, size_t(nt), tmp);
+  return observe_slots(c, slots, 0, o, bond, occ_buf);
+}
+
+int ocg_observe_states(ocg_ctx* c, int n, const int* dims, const double* const* data, const int* rows, int nrows,
+                       double* norm2, double* occ, int* bond, double* corr_ada, double* corr_nn) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm)
+    return hb(c, hbm_observe_states(c->hbm, n, dims, data, rows, nrows, norm2, occ, bond, corr_ada, corr_nn));
+  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
+  if (int rc = observe_check_rows(c, rows, nrows)) return rc;
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const OcgParams& P = c->P;
+  const obs::Outputs o{norm2, occ, corr_ada, corr_nn, P.L, P.p, nrows, rows};
+  std::vector<double> tmp;
+  double* occ_buf = observe_prepare(o, size_t(n), tmp);
+  // staged in the scratch slots after the trajectory slots, as ocg_step_batch, a batch at a time
+  const int base = 6 + 4 * c->N, B = std::min(n, 64);
+  if (int rc = ensure_slots(c, base + B)) return rc;
+  for (int i0 = 0; i0 < n; i0 += B) {
+    const int nb = std::min(B, n - i0);
+    std::vector<int> slots(nb);
+    for (int i = 0; i < nb; ++i) {
+      slots[i] = base + i;
+      if (int rc = upload_mps(c, slots[i], dims + size_t(i0 + i) * P.nsq, data[i0 + i])) return rc;
+    }
+    if (int rc = observe_slots(c, slots, size_t(i0), o, bond, occ_buf)) return rc;
+  }
+  return 0;
+}
+
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,
                      long* sweep_steps) {
-  if (!c || kind < 0 || kind > 8) return OCG_EINVAL;
+  if (!c || kind < 0 || kind > 9) return OCG_EINVAL;
   if (kind == 8) {  // getHessian path counters (HBM engine; zeros on the LDS engine)
     if (total_ms) *total_ms = 0;
     if (launches) *launches = c->pipe_runs;
@@ -1808,6 +1994,14 @@ int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, dou
     if (launches) *launches = 0;
     if (alg_bytes) *alg_bytes = 0;
     if (alg_flops) *alg_flops = 0;
+    if (sweep_steps) *sweep_steps = 0;
+    return 0;
+  }
+  if (kind == 9) {  // the observable kernels (observe.hpp): traffic from the host's task lists
+    if (total_ms) *total_ms = c->kst[9].ms;
+    if (launches) *launches = c->obs_tr.launches;
+    if (alg_bytes) *alg_bytes = c->obs_tr.bytes;
+    if (alg_flops) *alg_flops = c->obs_tr.flops;
     if (sweep_steps) *sweep_steps = 0;
     return 0;
   }
@@ -1851,6 +2045,7 @@ int ocg_reset_stats(ocg_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->d_stats, 0, sizeof(double) * 24, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (auto& k : c->kst) k = KStat{};
+  c->obs_tr = obs::Traffic{};
   return 0;
 }
 

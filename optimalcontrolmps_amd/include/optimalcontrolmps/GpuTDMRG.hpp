@@ -269,6 +269,31 @@ class GpuTDMRG::Engine {
     for (size_t i = 0; i < M; ++i) std::copy(hc.begin() + i * M, hc.begin() + (i + 1) * M, Hc[i].begin());
     return Hc;
   }
+  // Observables of the device-resident trajectory (ocg_observe): which 0 psi_t,
+  // 1 xi_t, 2 xiHlist; ts the state indices (empty: all N), rows the start
+  // sites (1..L) of the correlation rows (empty: none).  Nothing but the
+  // results leaves the device.
+  TrajectoryObservables observe(int which = 0, const std::vector<int>& ts = {}, const std::vector<int>& rows = {}) {
+    TrajectoryObservables o;
+    o.L = stepper.L;
+    o.p = stepper.p;
+    o.ts = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) o.ts.push_back(int(t));
+    o.rows = rows;
+    const size_t nt = o.ts.size(), nr = rows.size(), L = size_t(o.L);
+    o.norm2.assign(nt, 0.0);
+    o.occ.assign(nt * L * o.p, 0.0);
+    o.bond.assign(nt * (L + 1), 0);
+    o.ada.assign(nt * nr * L, Cplx(0, 0));
+    o.nn.assign(nt * nr * L, 0.0);
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_observe(c, which, o.ts.data(), int(nt), rows.data(), int(nr), o.norm2.data(), o.occ.data(),
+                              o.bond.data(), nr ? reinterpret_cast<double*>(o.ada.data()) : nullptr,
+                              nr ? o.nn.data() : nullptr),
+                  c, "ocg_observe");
+    return o;
+  }
   std::vector<MPS> psiTrajectory() {
     std::vector<MPS> out;
     for (size_t t = 0; t < N; ++t)

@@ -72,4 +72,33 @@ struct MPS {
   const double* raw() const { return reinterpret_cast<const double*>(data.data()); }
 };
 
+// Observables of nt trajectory states evaluated on the device (ocg_observe,
+// include/ocmps.h): what GpuTDMRG::Engine::observe and
+// OptimalControl::getPsitObservables return and the overloads of
+// correlations.hpp read.  Entry e belongs to trajectory state ts[e].
+struct TrajectoryObservables {
+  int L = 0, p = 0;
+  std::vector<int> ts;        // [e] state index
+  std::vector<int> rows;      // start sites (1..L) of the correlation rows
+  std::vector<double> norm2;  // [e] <psi|psi>
+  std::vector<double> occ;    // [e][L][p] occupation distribution (raw: sums to norm2 per site)
+  std::vector<int> bond;      // [e][L+1] bond dimensions
+  std::vector<Cplx> ada;      // [e][row][L] <a+_i a_j>, j >= i (0 for j < i)
+  std::vector<double> nn;     // [e][row][L] <n_i n_j>, j >= i
+  size_t size() const { return ts.size(); }
+  double occAt(size_t e, int site, int n) const { return occ[(e * L + (site - 1)) * p + n]; }
+  int bondDim(size_t e, int b) const { return bond[e * (L + 1) + b]; }
+  int maxBondDim(size_t e) const {
+    int m = 0;
+    for (int b = 0; b <= L; ++b) m = m < bondDim(e, b) ? bondDim(e, b) : m;
+    return m;
+  }
+  // index of start site i among rows, -1 if it was not requested
+  int rowOf(int i) const {
+    for (size_t r = 0; r < rows.size(); ++r)
+      if (rows[r] == i) return int(r);
+    return -1;
+  }
+};
+
 }  // namespace ocmps

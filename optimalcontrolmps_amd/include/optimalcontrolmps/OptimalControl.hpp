@@ -12,6 +12,7 @@
 //   Engine: setShards(n), propagate(u, which), divT(), overlapFactor(),
 //           fidelities(), precomputeXiH(), hessianRows(u, F, divT, H),
 //           hessianFresh(u, F&, divT&, H) (all of the above for a new control), psiTrajectory(),
+//           observe(which, ts, rows) (optional: getPsitObservables needs it),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -55,6 +56,15 @@ class OptimalControl {
   }
 
   std::vector<MPS> getPsit() const { return engine->psiTrajectory(); }
+  // The drivers' loops over getPsit() without the states leaving the device:
+  // occupation distributions, bond dimensions and a+a / nn correlation rows of
+  // psi_t for t in ts (empty: all), rows = start sites 1..L (correlations.hpp
+  // has the reference-named overloads that read the result).  Only for
+  // steppers whose Engine has observe() (GpuTDMRG).
+  ocmps::TrajectoryObservables getPsitObservables(const std::vector<int>& ts = {},
+                                                  const std::vector<int>& rows = {}) const {
+    return engine->observe(0, ts, rows);
+  }
   size_t getM() const { return M; }
   size_t getN() const { return N; }
   stdvec getControl(const stdvec& control) { return GRAPE ? control : basis.convertControl(control); }

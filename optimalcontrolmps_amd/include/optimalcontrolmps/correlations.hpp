@@ -14,7 +14,11 @@
 // Site operators as include/BH_sites.h:114-176 defines them: "N", "A", "Adag",
 // "N(N-1)", "NN" and "Id" (which, like the reference's, has no n = 0 entry).
 //
-// Host code (these are analysis calls, not the optimisation's hot path).  The
+// The overloads taking a TrajectoryObservables read what the device computed
+// for the stored trajectory (OptimalControl::getPsitObservables): the loops
+// over getPsit() of the drivers without copying a state to the host.
+//
+// The MPS functions are host code (analysis of single states).  The
 // contractions are exact and gauge-free: left and right environments are
 // both formed, so any MPS the engine returns (trajectory states carry their
 // orthogonality centre on site 2) gives the reference's value for a
@@ -307,6 +311,56 @@ inline std::vector<std::vector<Cplx>> correlationMatrix(const BoseHubbard& sites
     }
   }
   return rho;
+}
+
+// ---- the same observables from the device's results (TrajectoryObservables,
+// ocg_observe): entry e of obs, i.e. trajectory state obs.ts[e].  Values are
+// raw like the functions above (not divided by the norm).
+inline std::vector<Cplx> expectationValues(const TrajectoryObservables& o, size_t e, const std::string& opname) {
+  if (e >= o.size()) throw std::invalid_argument("expectationValues: entry out of range");
+  const std::vector<double> O = obs::siteOp(opname, o.p);  // validates the name
+  std::vector<Cplx> out(o.L, Cplx(0, 0));
+  for (int i = 1; i <= o.L; ++i) {
+    double s = 0;
+    for (int n = 0; n < o.p; ++n) s += O[size_t(n) * o.p + n] * o.occAt(e, i, n);
+    out[i - 1] = s;  // "A" / "Adag" have no diagonal: exactly 0 by particle conservation
+  }
+  return out;
+}
+
+// rho_ij from the rows of obs ("Adag","A" or "N","N"; every start site 1..L
+// must have been requested), mirrored rho_ji = conj(rho_ij), real diagonal
+inline std::vector<std::vector<Cplx>> correlationMatrix(const TrajectoryObservables& o, size_t e,
+                                                        const std::string& opname1, const std::string& opname2) {
+  if (e >= o.size()) throw std::invalid_argument("correlationMatrix: entry out of range");
+  const bool ada = opname1 == "Adag" && opname2 == "A", nn = opname1 == "N" && opname2 == "N";
+  if (!ada && !nn)
+    throw std::invalid_argument("correlationMatrix(TrajectoryObservables): only (\"Adag\", \"A\") and (\"N\", \"N\")");
+  const size_t N = size_t(o.L), R = o.rows.size();
+  std::vector<std::vector<Cplx>> rho(N, std::vector<Cplx>(N, Cplx(0, 0)));
+  for (int i = 1; i <= o.L; ++i) {
+    const int r = o.rowOf(i);
+    if (r < 0) throw std::invalid_argument("correlationMatrix: start site " + std::to_string(i) + " was not observed");
+    for (int j = i; j <= o.L; ++j) {
+      const size_t at = (e * R + size_t(r)) * N + size_t(j - 1);
+      const Cplx c = ada ? o.ada[at] : Cplx(o.nn[at], 0.0);
+      rho[i - 1][j - 1] = i == j ? Cplx(c.real(), 0.0) : c;
+      if (j > i) rho[j - 1][i - 1] = std::conj(c);
+    }
+  }
+  return rho;
+}
+
+// largest eigenvalue of that matrix (host heev on the L x L matrix)
+inline double correlationTerm(const TrajectoryObservables& o, size_t e, const std::string& opname1 = "Adag",
+                              const std::string& opname2 = "A") {
+  const auto rho = correlationMatrix(o, e, opname1, opname2);
+  const int N = int(rho.size());
+  obs::cmat A(size_t(N) * N);
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) A[size_t(i) * N + j] = rho[i][j];
+  const std::vector<double> w = obs::heev(A, N);
+  return *std::max_element(w.begin(), w.end());
 }
 
 // largest eigenvalue of the correlation matrix (diagHermitian, Maxm 1; :80-98)

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("OCG_LIB", os.path.join(PKG_DIR, LIB_NAME))
 CSRC = os.path.join(PKG_DIR, "csrc")
 HEADER = os.path.join(ROOT, "include", "ocmps.h")
 
-OCG_ERRORS = {1: "EINVAL", 2: "ECAP", 3: "EHIP", 4: "ESTATE", 5: "ENUM"}
+OCG_ERRORS = {1: "EINVAL", 2: "ECAP", 3: "EHIP", 4: "ESTATE", 5: "ENUM", 6: "ENOMEM"}
 
 
 class OcgError(RuntimeError):
@@ -44,8 +44,8 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
         flags.append(f"-DOCG_NT={int(nt)}")
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
-                  "fast.hpp", "fast_plan.hpp", "fast_chain.hpp"],
-        "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp"],
+                  "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp"],
+        "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -125,6 +125,8 @@ SIGNATURES = [
     ("ocg_gradient_multi", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, dp, dp]),
     ("ocg_gradient", C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     ("ocg_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_size_t, szp]),
+    ("ocg_observe", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, ip, C.c_int, dp, dp, ip, dp, dp]),
+    ("ocg_observe_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), ip, C.c_int, dp, dp, ip, dp, dp]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -444,6 +446,54 @@ class Engine:
         self._chk(lib().ocg_get_state(self.h, which, t, fd.ctypes.data_as(ip), d.ctypes.data_as(dp), self.cap,
                                       C.byref(n)), "ocg_get_state")
         return self._wrap(fd, d, n)
+
+    OBSERVE_OUTPUTS = ("norm2", "occ", "bond", "ada", "nn")
+
+    def _observe_out(self, n, nrows, outputs):
+        L, p = self.L, self.p
+        bad = set(outputs) - set(self.OBSERVE_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown observe outputs {sorted(bad)}")
+        full = {"norm2": lambda: np.zeros(n), "occ": lambda: np.zeros((n, L, p)),
+                "bond": lambda: np.zeros((n, L + 1), np.int32),
+                "ada": lambda: np.zeros((n, nrows, L), np.complex128), "nn": lambda: np.zeros((n, nrows, L))}
+        return {k: full[k]() for k in self.OBSERVE_OUTPUTS if k in outputs}
+
+    @staticmethod
+    def _observe_ptrs(out, nrows):
+        """the five output pointers of ocg_observe; NULL (skipped, its work not done) for what is not asked for"""
+        def ptr(k, t):
+            return out[k].ctypes.data_as(t) if k in out and (nrows or k not in ("ada", "nn")) else None
+        return ptr("norm2", dp), ptr("occ", dp), ptr("bond", ip), ptr("ada", dp), ptr("nn", dp)
+
+    def observe(self, which=0, ts=None, rows=(), outputs=OBSERVE_OUTPUTS):
+        """Observables of the device trajectory states (ocg_observe): which 0 psi_t,
+        1 xi_t, 2 xiH_t; ts state indices (default all), rows start sites in 1..L.
+        Returns a dict of numpy arrays: norm2 (nt,), occ (nt, L, p) (raw, not divided
+        by norm2), bond (nt, L+1), ada (nt, nrows, L) complex = <a+_i a_j> and nn
+        (nt, nrows, L) = <n_i n_j>, both for j >= i (entries j < i are 0).  `outputs`
+        selects a subset of these: what is left out is not computed."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        rr, pr = _i(list(rows))
+        out = self._observe_out(len(tt), len(rr), outputs)
+        self._chk(lib().ocg_observe(self.h, int(which), pt, len(tt), pr, len(rr), *self._observe_ptrs(out, len(rr))),
+                  "ocg_observe")
+        return out
+
+    def observe_states(self, states, rows=(), outputs=OBSERVE_OUTPUTS):
+        """The observables of observe() for caller-supplied host states (any gauge or
+        norm), staged on the device in batches (ocg_observe_states)."""
+        n = len(states)
+        rr, pr = _i(list(rows))
+        out = self._observe_out(n, len(rr), outputs)
+        if n == 0:
+            return out
+        dims = np.ascontiguousarray(np.concatenate([m.dims for m in states]).astype(np.int32))
+        raws = [np.ascontiguousarray(m.raw()) for m in states]
+        data = (dp * n)(*[r.ctypes.data_as(dp) for r in raws])
+        self._chk(lib().ocg_observe_states(self.h, n, dims.ctypes.data_as(ip), data, pr, len(rr),
+                                           *self._observe_ptrs(out, len(rr))), "ocg_observe_states")
+        return out
 
     def stats(self, kind):
         ms = C.c_double(); n = C.c_long(); b = C.c_double(); f = C.c_double(); s = C.c_long()

@@ -1,0 +1,145 @@
+"""Wall time of the device observables (ocg_observe) against the only path there
+was before: one ocg_get_state copy per state (a lower bound of that path, which
+adds the host contraction of correlations.hpp on top).
+
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|all] [--reps R] [--out DIR]
+
+One process; every shape is warmed up; each timed call ends in a device
+synchronise (both entry points return only after their results are on the
+host); the two paths alternate and the spread (min / median / max) is
+reported.  Config 1: L=5, p=5, chi<=80, N_t=201, the LDS engine.  Config 4
+slice: L=20, p=7, chi=256 from the warm state, N_t=33, the HBM engine; also the
+old path's cost for one state (copy + host expectationValues).  Writes
+observe_config1.json / observe_config4.json into --out (default profiles/).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import tempfile
+import time
+
+import numpy as np
+
+from optimalcontrolmps_amd import native
+from optimalcontrolmps_amd.native import MPS, Engine
+
+ROOT = native.ROOT
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return {"min_ms": 1e3 * xs[0], "median_ms": 1e3 * xs[len(xs) // 2], "max_ms": 1e3 * xs[-1], "reps": len(xs)}
+
+
+def copy_all(eng, which, n, dims, data):
+    """the n ocg_get_state copies alone, into preallocated buffers"""
+    got = C.c_size_t(0)
+    for t in range(n):
+        eng._chk(native.lib().ocg_get_state(eng.h, which, t, dims.ctypes.data_as(native.ip),
+                                            data.ctypes.data_as(native.dp), eng.cap, C.byref(got)), "ocg_get_state")
+
+
+def timed(f):
+    t0 = time.perf_counter()
+    f()
+    return time.perf_counter() - t0
+
+
+def config1(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    eng.propagate(np.linspace(2.5, 50.0, Nt), 1)
+    dims = np.zeros((L + 1) * (Q + 1), np.int32)
+    data = np.zeros(2 * eng.cap)
+    rows = list(range(1, L + 1))
+    cases = {"occ_only": lambda: eng.observe(0, None, (), outputs=("occ",)),
+             "all_rows": lambda: eng.observe(0, None, rows),
+             "get_state_copies": lambda: copy_all(eng, 0, Nt, dims, data)}
+    for f in cases.values():  # warm up every shape
+        f()
+        f()
+    eng.reset_stats()
+    t = {k: [] for k in cases}
+    for _ in range(reps):     # alternating
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine", "fast_chain": int(eng.info.fast_chain),
+           "bond_max": int(eng.observe(0, None, (), outputs=("bond",))["bond"].max())}
+    res.update({k: spread(v) for k, v in t.items()})
+    res["kind9"] = eng.stats(9)
+    for k in ("occ_only", "all_rows"):
+        res[k + "_vs_copies"] = res["get_state_copies"]["median_ms"] / res[k]["median_ms"]
+    return res
+
+
+def host_expectation_seconds(state):
+    """copy-free part of the old path for one state: expectationValues(sites, psi, "N") on the host"""
+    src = os.path.join(native.PKG_DIR, "tools", "host_expectation_timing.cpp")
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "host_expectation_timing")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, src])
+        path = os.path.join(d, "state.bin")
+        with open(path, "wb") as f:
+            f.write(np.array([state.L, state.p, state.Q, state.dims.size, state.data.size], np.int32).tobytes())
+            f.write(state.dims.tobytes() + state.data.tobytes())
+        return json.loads(subprocess.run([exe, path], capture_output=True, text=True, check=True).stdout)
+
+
+def config4(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 20, 7, 20, 1.0, 0.005, 1e-8, 256, 33
+    z = np.load(os.path.join(GOLDEN, "c4_warm256.npz"), allow_pickle=False)
+    c4 = np.load(os.path.join(GOLDEN, "c4.npz"), allow_pickle=False)
+    u = np.load(os.path.join(GOLDEN, "c4_w256h33.npz"), allow_pickle=False)["u"]
+    eng = Engine(L, p, Q, J, dt, cut, maxm, engine="hbm")
+    eng.set_states(MPS(L, p, Q, c4["w256h/tgt_dims"], c4["w256h/tgt_data"]), MPS(L, p, Q, z["dims"], z["data"]))
+    eng.propagate(u, 1)
+    dims = np.zeros((L + 1) * (Q + 1), np.int32)
+    data = np.zeros(2 * eng.cap)
+    cases = {"observe_rows10": lambda: eng.observe(0, None, [10]),
+             "get_state_copies": lambda: copy_all(eng, 0, Nt, dims, data)}
+    for f in cases.values():
+        f()
+    eng.reset_stats()
+    t = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    k9, k7 = eng.stats(9), eng.stats(7)
+    res = {"config": "4 slice: L=20 p=7 Q=20 chi=256 (warm state) N_t=33, HBM engine, rows=[10]"}
+    res.update({k: spread(v) for k, v in t.items()})
+    res["per_state_ms"] = res["observe_rows10"]["median_ms"] / Nt
+    res["kind9_per_call"] = {k: v / reps for k, v in k9.items()}
+    res["k_gemm_share_of_kind9_time"] = k7["ms"] / k9["ms"] if k9["ms"] else None
+    res["kind9_tflops"] = 1e-9 * k9["alg_flops"] / k9["ms"] if k9["ms"] else None
+    res["old_path_one_state"] = {"get_state_ms": res["get_state_copies"]["median_ms"] / Nt,
+                                 "host_expectationValues_N": host_expectation_seconds(eng.state(0, Nt // 2))}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="all", choices=["1", "4", "all"])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4))):
+        if a.config in (name, "all"):
+            res = fn(reps)
+            res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
+            with open(os.path.join(a.out, f"observe_config{name}.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
