@@ -2281,6 +2281,8 @@ struct hbm_engine {
   int psi_base() const { return 4; }
   int xi_base() const { return 4 + N; }
   int xih_base() const { return 4 + 2 * N; }
+  // slots of the three trajectories of n states: the above and two scratch slots behind xiH_t
+  static long traj_slots(int n) { return 4 + 3L * n + 2; }
   double ms[10] = {0};
   long launches[10] = {0};
   long steps[10] = {0};
@@ -2343,6 +2345,232 @@ struct Timer {
     h->steps[kind] += nsteps;
   }
 };
+
+// A call that grows the state heap for slots it does not keep gives them back,
+// down to `keep` slots: on success inside the guard (done(): a device failure
+// there is the call's status), on failure from the destructor, errors swallowed
+// while the guard unwinds, so later memory decisions (hipMemGetInfo) see the
+// HBM free.  The pipelined getHessian keeps what it grew for its next call
+// (kept()); when it fails (pipe) it also gives back the two worker engines with
+// their pools and arenas and the chains the context engine's pool grew by, so
+// that the two-phase path ocg_hessian may retry sees that memory free.
+struct GiveBack {
+  hbm_engine* h;
+  size_t keep;
+  bool pipe;
+  int chains0;
+  bool ok = false;
+  GiveBack(hbm_engine* h_, size_t keep_, bool pipe_ = false)
+      : h(h_), keep(keep_), pipe(pipe_), chains0(h_->E->nchain_cap) {}
+  void kept() { ok = true; }
+  void done() {
+    ok = true;
+    h->E->shrink_states(keep);
+  }
+  ~GiveBack() {
+    if (ok) return;
+    hbm::Engine& E = *h->E;
+    try {
+      E.drain();
+      if (pipe) {
+        for (auto& W : h->W)
+          if (W) {
+            W->drain();
+            W.reset();
+          }
+        E.release_all();
+        E.shrink_chains(chains0);
+      }
+      E.shrink_states(keep);
+    } catch (...) {
+    }
+  }
+};
+
+// A leg: a chain on its way through a control's time grid, from time t to time
+// end, forward (u[t] -> u[t+1]) or backward (u[t] -> u[t-1]).
+struct Leg {
+  Chain* c;
+  const double* u;
+  int t, end;
+  bool fwd;
+};
+// One Engine::step, as a single batch on engine E, of every leg that has not
+// reached its end; returns the legs that moved (their t already advanced).
+// Where the states go (store_many, overlaps) is the caller's loop body.
+std::vector<int> step_legs(hbm::Engine& E, std::vector<Leg>& legs) {
+  std::vector<Chain*> c;
+  std::vector<double> uf, ut;
+  std::vector<int> fw, moved;
+  for (size_t i = 0; i < legs.size(); ++i) {
+    Leg& g = legs[i];
+    if (g.fwd ? g.t >= g.end : g.t <= g.end) continue;
+    const int to = g.fwd ? g.t + 1 : g.t - 1;
+    c.push_back(g.c);
+    uf.push_back(g.u[g.t]);
+    ut.push_back(g.u[to]);
+    fw.push_back(g.fwd ? 1 : 0);
+    moved.push_back(int(i));
+    g.t = to;
+  }
+  E.step(c, uf, ut, fw);
+  return moved;
+}
+// the chains of the legs `moved` into the heap slots slot(leg, its time); a slot < 0 is skipped
+template <class F>
+void store_legs(hbm::Engine& W, std::vector<State>& heap, const std::vector<Leg>& legs, const std::vector<int>& moved,
+                F slot) {
+  std::vector<State*> ss;
+  std::vector<Chain*> cc;
+  for (int i : moved) {
+    const int s = slot(i, legs[i].t);
+    if (s < 0) continue;
+    ss.push_back(&heap[s]);
+    cc.push_back(legs[i].c);
+  }
+  if (!ss.empty()) W.store_many(ss, cc);
+}
+// every leg's chain loaded from its view in `from`, its starting state stored in slot(leg, its time)
+template <class F>
+void start_legs(hbm::Engine& W, std::vector<State>& heap, const std::vector<Leg>& legs, const std::vector<View>& from,
+                F slot) {
+  std::vector<Chain*> cs;
+  std::vector<int> all;
+  for (size_t i = 0; i < legs.size(); ++i) { cs.push_back(legs[i].c); all.push_back(int(i)); }
+  W.load_many(cs, from);
+  store_legs(W, heap, legs, all, slot);
+}
+// every leg to its end in lockstep, each new state stored in slot(leg, its time)
+template <class F>
+void run_legs(hbm::Engine& E, std::vector<Leg>& legs, F slot) {
+  for (;;) {
+    const std::vector<int> moved = step_legs(E, legs);
+    if (moved.empty()) break;
+    store_legs(E, E.states, legs, moved, slot);
+  }
+}
+
+// divT_t everywhere and F without keeping the trajectories: psi forward and xi
+// backward run as one lockstep batch and meet in the middle.  Phase 1 stores
+// psi_0..psi_tm and xi_{N-1}..xi_{tm+1} (tm = (N-1)/2) in the slots half(t);
+// phase 2 carries psi on to N-1, each new psi_t paired with the stored xi_t, and
+// xi down to 0, each new xi_t paired with the stored psi_t.  N states instead of
+// the stored path's 2N (config 5 at N_t = 1001: 205 GB instead of 410 GB), the
+// same N-1 dependent steps per chain, and the same states, overlaps and numbers
+// bit for bit (every HBM-engine kernel is batch-independent and deterministic).
+// ckpt_psi(t) / ckpt_xi(t): a slot that also takes psi_t / xi_t on the way, or -1.
+// Fills dv (N entries) and Fc; returns the steps taken.
+template <class Half, class CkPsi, class CkXi>
+long meet_in_the_middle(hbm::Engine& E, const double* u, int N, Half half, CkPsi ckpt_psi, CkXi ckpt_xi,
+                        std::vector<std::complex<double>>& dv, std::complex<double>& Fc) {
+  const int tm = (N - 1) / 2;
+  Chain* cp = E.acquire(false);
+  Chain* cx = E.acquire(false);
+  std::vector<Leg> legs{{cp, u, 0, tm, true}, {cx, u, N - 1, tm + 1, false}};
+  std::vector<Chain*> both{cp, cx};
+  E.load_many(both, {E.states[0].view(), E.states[1].view()});
+  auto ckpt = [&](int leg, int t) { return leg == 0 ? ckpt_psi(t) : ckpt_xi(t); };
+  // every state of phase 1 into its half slot and, where there is one, its checkpoint slot
+  auto store = [&](const std::vector<int>& legs_in) {
+    std::vector<State*> ss;
+    std::vector<Chain*> cc;
+    for (int i : legs_in) {
+      ss.push_back(&E.states[half(legs[i].t)]);
+      cc.push_back(legs[i].c);
+      if (ckpt(i, legs[i].t) >= 0) { ss.push_back(&E.states[ckpt(i, legs[i].t)]); cc.push_back(legs[i].c); }
+    }
+    E.store_many(ss, cc);
+  };
+  store({0, 1});
+  long nsteps = 0;
+  // phase 1: psi 0 -> tm, xi N-1 -> tm+1, both stored
+  for (;;) {
+    const std::vector<int> moved = step_legs(E, legs);
+    if (moved.empty()) break;
+    nsteps += long(moved.size());
+    store(moved);
+  }
+  // phase 2: psi tm -> N-1 against the stored xi_t, xi tm+1 -> 0 against the stored psi_t
+  legs[0].end = N - 1;
+  legs[1].end = 0;
+  for (;;) {
+    const std::vector<int> moved = step_legs(E, legs);
+    if (moved.empty()) break;
+    nsteps += long(moved.size());
+    store_legs(E, E.states, legs, moved, ckpt);
+    std::vector<View> xs, ys;  // divT_t = overlapC(xi_t, dH, psi_t) (src/OptimalControl.cpp:409-419)
+    for (int i : moved) {
+      const View stored = E.states[half(legs[i].t)].view();
+      xs.push_back(i == 0 ? stored : cx->view());
+      ys.push_back(i == 0 ? cp->view() : stored);
+    }
+    const auto r = E.overlaps(xs, ys, true);
+    for (size_t k = 0; k < moved.size(); ++k) dv[legs[moved[k]].t] = r[k];
+  }
+  // F = overlapC(psi_{N-1}, target) (:242); the two end points of the trajectories
+  // (divT_{N-1} with xi_{N-1} = target, divT_0 with psi_0 = init) came from phase 2
+  Fc = E.overlaps({cp->view()}, {E.states[1].view()}, false)[0];
+  E.sync();
+  E.release(cp);
+  E.release(cx);
+  return nsteps;
+}
+
+std::vector<View> views_of(const std::vector<Chain*>& cs) {
+  std::vector<View> vs;
+  for (auto* c : cs) vs.push_back(c->view());
+  return vs;
+}
+
+// out slot out0 + i = dH applied to slot in0 + i, i < n, of `heap` on engine W,
+// B states per batch (exactApplyMPO(dH, .), src/OptimalControl.cpp:300-303);
+// abort: the pipeline's flag, looked at before every batch
+void dH_slots(hbm::Engine& W, std::vector<State>& heap, int in0, int out0, int n, int B,
+              const std::atomic<int>* abort = nullptr) {
+  for (int t0 = 0; t0 < n && !(abort && abort->load()); t0 += B) {
+    const int nb = std::min(B, n - t0);
+    std::vector<View> in;
+    std::vector<Chain*> out;
+    std::vector<State*> ss;
+    for (int i = 0; i < nb; ++i) {
+      in.push_back(heap[in0 + t0 + i].view());
+      out.push_back(W.acquire(false));
+      ss.push_back(&heap[out0 + t0 + i]);
+    }
+    W.apply_dH(in, out);
+    W.store_many(ss, out);
+    W.sync();
+    for (auto* c : out) W.release(c);
+  }
+}
+
+// rows joining: psiH_i = dH psi_i into chains acquired on W (appended to out) and
+// normiH = |psiH_i| (src/OptimalControl.cpp:256-257)
+std::vector<double> join_rows(hbm::Engine& W, const std::vector<View>& in, std::vector<Chain*>& out) {
+  for (size_t i = 0; i < in.size(); ++i) out.push_back(W.acquire(false));
+  W.apply_dH(in, out);
+  std::vector<double> nrm = W.site_norm2(views_of(out), 1);
+  for (double& x : nrm) x = std::sqrt(std::max(0.0, x));
+  return nrm;
+}
+
+// The Hessian's entries (src/OptimalControl.cpp:259-264, :266-278).  Every
+// getHessian path writes them through these, which is what keeps the paths
+// equal bit for bit.
+using cplx = std::complex<double>;
+inline double hess_diag(double dt2, cplx Fc, cplx ov, cplx dvi) {
+  const double v1 = (Fc * ov).real(), v2 = -std::norm(dvi);
+  return dt2 * (v1 + v2);
+}
+inline double hess_offdiag(double dt2, cplx Fc, cplx ov, double nrm, cplx dvi, cplx dvj) {
+  const double v1 = (Fc * ov * nrm).real();
+  const double v2 = -(dvi * std::conj(dvj)).real();
+  return dt2 * (v1 + v2);
+}
+inline void hess_set(double* H, int N, int i, int j, double r) {
+  H[size_t(i) * N + j] = r;
+  H[size_t(j) * N + i] = r;
+}
 }  // namespace
 
 int hbm_create(int device, int L, int p, int npart, double J, double tstep, double cutoff, int maxm,
@@ -2440,7 +2668,7 @@ int hbm_overlap(hbm_engine* h, const int* dx, const double* x, const int* dy, co
   return guard(h, [&] {
     hbm::Engine& E = *h->E;
     E.set_caps(std::max(widest_of(E, dx), widest_of(E, dy)));
-    E.reserve_states(size_t(h->xih_base() + h->N + 2));
+    E.reserve_states(size_t(h->traj_slots(h->N)));
     const int sb = h->xih_base() + h->N;
     E.upload_state(E.states[sb], dx, x);
     E.upload_state(E.states[sb + 1], dy, y);
@@ -2497,7 +2725,7 @@ static void hbm_prepare_N(hbm_engine* h, int N) {
     h->N = N;
     h->have_psi = h->have_xi = h->have_xih = false;
   }
-  h->E->reserve_states(size_t(h->xih_base() + N + 2));
+  h->E->reserve_states(size_t(h->traj_slots(N)));
 }
 
 int hbm_propagate(hbm_engine* h, const double* u, int N, int which) {
@@ -2508,33 +2736,17 @@ int hbm_propagate(hbm_engine* h, const double* u, int N, int which) {
     if (which & 2) h->have_xi = h->have_xih = false;
     hbm::Engine& E = *h->E;
     E.reserve_chains(std::max(E.nchain_cap, 2), false);
-    std::vector<Chain*> cs;
-    std::vector<int> kind;  // 0 psi, 1 xi
-    if (which & 1) { cs.push_back(E.acquire(false)); kind.push_back(0); }
-    if (which & 2) { cs.push_back(E.acquire(false)); kind.push_back(1); }
+    std::vector<Leg> legs;  // psi from init forward, xi from the target backward
     std::vector<View> vs;
-    for (int k : kind) vs.push_back(E.states[k == 0 ? 0 : 1].view());
-    E.load_many(cs, vs);
-    std::vector<State*> ss;
-    for (int k : kind) ss.push_back(&E.states[k == 0 ? h->psi_base() : h->xi_base() + N - 1]);
-    E.store_many(ss, cs);
+    if (which & 1) { legs.push_back({E.acquire(false), u, 0, N - 1, true}); vs.push_back(E.states[0].view()); }
+    if (which & 2) { legs.push_back({E.acquire(false), u, N - 1, 0, false}); vs.push_back(E.states[1].view()); }
+    auto slot = [&](int i, int t) { return (legs[i].fwd ? h->psi_base() : h->xi_base()) + t; };
+    start_legs(E, E.states, legs, vs, slot);
     Timer t(h, 0);
-    std::vector<double> uf(cs.size()), ut(cs.size());
-    std::vector<int> fw(cs.size());
-    for (int s = 0; s + 1 < N; ++s) {
-      for (size_t i = 0; i < cs.size(); ++i) {
-        if (kind[i] == 0) { uf[i] = u[s]; ut[i] = u[s + 1]; fw[i] = 1; }
-        else { uf[i] = u[N - 1 - s]; ut[i] = u[N - 2 - s]; fw[i] = 0; }
-      }
-      E.step(cs, uf, ut, fw);
-      ss.clear();
-      for (size_t i = 0; i < cs.size(); ++i)
-        ss.push_back(&E.states[kind[i] == 0 ? h->psi_base() + s + 1 : h->xi_base() + N - 2 - s]);
-      E.store_many(ss, cs);
-    }
+    run_legs(E, legs, slot);
     E.sync();
-    t.stop(long(cs.size()) * (N - 1));
-    for (auto* c : cs) E.release(c);
+    t.stop(long(legs.size()) * (N - 1));
+    for (auto& g : legs) E.release(g.c);
     if (which & 1) { h->have_psi = true; }
     if (which & 2) { h->have_xi = true; h->have_xih = false; }
   });
@@ -2580,37 +2792,7 @@ int hbm_div_t(hbm_engine* h, double* divT) {
 }
 
 // getAnalyticGradient's device part (divT_t, F) without keeping the
-// trajectories: psi forward and xi backward run as one lockstep batch and meet
-// in the middle.  Phase 1 stores psi_0..psi_tm and xi_{N-1}..xi_{tm+1}
-// (tm = (N-1)/2); phase 2 carries psi on to N-1, each new psi_t paired with the
-// stored xi_t, and xi down to 0, each new xi_t paired with the stored psi_t.
-// N states instead of the stored path's 2N (config 5 at N_t = 1001: 205 GB
-// instead of 410 GB), the same N-1 dependent steps per chain, and the same
-// states, overlaps and numbers bit for bit (every HBM-engine kernel is
-// batch-independent and deterministic).  Leaves no device trajectories.
-// A call that grows the state heap for slots it does not keep gives them back,
-// down to the heap it began with, on success (done(): a device failure there is
-// the call's status) and on failure (the destructor, errors swallowed while the
-// guard unwinds), so later memory decisions (hipMemGetInfo) see the HBM free.
-struct HeapRestore {
-  hbm::Engine& E;
-  size_t keep;
-  bool ok = false;
-  explicit HeapRestore(hbm::Engine& e) : E(e), keep(e.heap_slots) {}
-  void done() {
-    ok = true;
-    E.shrink_states(keep);
-  }
-  ~HeapRestore() {
-    if (ok) return;
-    try {
-      E.drain();
-      E.shrink_states(keep);
-    } catch (...) {
-    }
-  }
-};
-
+// trajectories (meet_in_the_middle).  Leaves no device trajectories.
 int hbm_gradient_mid(hbm_engine* h, const double* u, int N, double* divT, double* F) {
   return guard(h, [&] {
     if (!h->have_states) throw hbm::Error(4, "ocg_set_states first");
@@ -2618,61 +2800,16 @@ int hbm_gradient_mid(hbm_engine* h, const double* u, int N, double* divT, double
     hbm::Engine& E = *h->E;
     h->have_psi = h->have_xi = h->have_xih = false;  // the trajectory slots are overwritten
     h->N = 0;
-    HeapRestore heap(E);  // the half trajectories are not kept (the footprint stayed at N + 2 slots)
+    // the half trajectories are not kept (the footprint stayed at N + 2 slots)
+    GiveBack heap(h, E.heap_slots);
     E.reserve_states(size_t(N) + 2);
-    const int tm = (N - 1) / 2;
     auto slot = [](int t) { return 2 + t; };  // psi_t for t <= tm, xi_t above
+    auto none = [](int) { return -1; };
     E.reserve_chains(std::max(E.nchain_cap, 2), false);
     Timer tt(h, 0);
-    Chain* cp = E.acquire(false);
-    Chain* cx = E.acquire(false);
-    std::vector<Chain*> both{cp, cx};
-    E.load_many(both, {E.states[0].view(), E.states[1].view()});
-    E.store_many({&E.states[slot(0)], &E.states[slot(N - 1)]}, both);
     std::vector<std::complex<double>> dv(N);
-    long nsteps = 0;
-    // one lockstep step of the chains still moving: psi t -> t+1 while t < pe,
-    // xi t -> t-1 while t > xe
-    auto advance = [&](int& tp, int pe, int& tx, int xe) {
-      std::vector<Chain*> c;
-      std::vector<double> uf, ut;
-      std::vector<int> fw;
-      if (tp < pe) { c.push_back(cp); uf.push_back(u[tp]); ut.push_back(u[tp + 1]); fw.push_back(1); }
-      if (tx > xe) { c.push_back(cx); uf.push_back(u[tx]); ut.push_back(u[tx - 1]); fw.push_back(0); }
-      E.step(c, uf, ut, fw);
-      nsteps += long(c.size());
-      if (tp < pe) ++tp;
-      if (tx > xe) --tx;
-    };
-    // phase 1: psi 0 -> tm, xi N-1 -> tm+1, both stored
-    int tp = 0, tx = N - 1;
-    while (tp < tm || tx > tm + 1) {
-      const bool mp = tp < tm, mx = tx > tm + 1;
-      advance(tp, tm, tx, tm + 1);
-      std::vector<State*> ss;
-      std::vector<Chain*> cc;
-      if (mp) { ss.push_back(&E.states[slot(tp)]); cc.push_back(cp); }
-      if (mx) { ss.push_back(&E.states[slot(tx)]); cc.push_back(cx); }
-      E.store_many(ss, cc);
-    }
-    // phase 2: psi tm -> N-1 against the stored xi_t, xi tm+1 -> 0 against the stored psi_t
-    while (tp < N - 1 || tx > 0) {
-      const bool mp = tp < N - 1, mx = tx > 0;
-      advance(tp, N - 1, tx, 0);
-      std::vector<View> xs, ys;  // divT_t = overlapC(xi_t, dH, psi_t) (src/OptimalControl.cpp:409-419)
-      if (mp) { xs.push_back(E.states[slot(tp)].view()); ys.push_back(cp->view()); }
-      if (mx) { xs.push_back(cx->view()); ys.push_back(E.states[slot(tx)].view()); }
-      const auto r = E.overlaps(xs, ys, true);
-      int k = 0;
-      if (mp) dv[tp] = r[k++];
-      if (mx) dv[tx] = r[k++];
-    }
-    // F = overlapC(psi_{N-1}, target) (:242); the two end points of the trajectories
-    // (divT_{N-1} with xi_{N-1} = target, divT_0 with psi_0 = init) came from phase 2
-    const std::complex<double> Fc = E.overlaps({cp->view()}, {E.states[1].view()}, false)[0];
-    E.sync();
-    E.release(cp);
-    E.release(cx);
+    std::complex<double> Fc;
+    const long nsteps = meet_in_the_middle(E, u, N, slot, none, none, dv, Fc);
     tt.stop(nsteps);
     F[0] = Fc.real();
     F[1] = Fc.imag();
@@ -2692,58 +2829,31 @@ int hbm_gradient_multi(hbm_engine* h, int K, const double* U, int N, double* div
     hbm_prepare_N(h, N);
     h->have_psi = h->have_xi = h->have_xih = false;
     hbm::Engine& E = *h->E;
-    const int extra0 = h->xih_base() + N + 2;
+    const int extra0 = int(h->traj_slots(N));
     auto pb = [&](int k) { return k == 0 ? h->psi_base() : extra0 + 2 * N * (k - 1); };
     auto xb = [&](int k) { return k == 0 ? h->xi_base() : extra0 + 2 * N * (k - 1) + N; };
     // the other controls' trajectories are not kept: their slots are given back
     // afterwards, on success and on failure, down to the heap the call began with
     // (a previous pipelined getHessian's row-state slots stay for its next call)
-    const size_t keep = std::max(size_t(extra0), E.heap_slots);
-    struct ShrinkOnError {  // unwinding only: the success path shrinks inside the guard
-      hbm::Engine& E;
-      size_t keep;
-      bool ok = false;
-      ~ShrinkOnError() {
-        if (ok) return;
-        try {
-          E.drain();
-          E.shrink_states(keep);
-        } catch (...) {
-        }
-      }
-    } shrink{E, keep};
+    GiveBack heap(h, std::max(size_t(extra0), E.heap_slots));
     E.reserve_states(size_t(extra0) + size_t(2) * N * (K - 1));
     E.reserve_chains(std::max(E.nchain_cap, 2 * K), false);
-    std::vector<Chain*> cs(2 * K);
-    std::vector<View> vs(2 * K);
-    std::vector<State*> ss(2 * K);
+    std::vector<Leg> legs;  // 2k: control k's psi, 2k + 1: its xi
+    std::vector<View> vs;
     for (int k = 0; k < K; ++k) {
-      cs[2 * k] = E.acquire(false);
-      cs[2 * k + 1] = E.acquire(false);
-      vs[2 * k] = E.states[0].view();      // psi_init
-      vs[2 * k + 1] = E.states[1].view();  // psi_target
-      ss[2 * k] = &E.states[pb(k)];
-      ss[2 * k + 1] = &E.states[xb(k) + N - 1];
+      const double* u = U + size_t(k) * N;
+      legs.push_back({E.acquire(false), u, 0, N - 1, true});
+      legs.push_back({E.acquire(false), u, N - 1, 0, false});
+      vs.push_back(E.states[0].view());  // psi_init
+      vs.push_back(E.states[1].view());  // psi_target
     }
-    E.load_many(cs, vs);
-    E.store_many(ss, cs);
+    auto slot = [&](int i, int t) { return (i % 2 == 0 ? pb(i / 2) : xb(i / 2)) + t; };
+    start_legs(E, E.states, legs, vs, slot);
     Timer t(h, 0);
-    std::vector<double> uf(2 * K), ut(2 * K);
-    std::vector<int> fw(2 * K);
-    for (int s = 0; s + 1 < N; ++s) {
-      for (int k = 0; k < K; ++k) {
-        const double* u = U + size_t(k) * N;
-        uf[2 * k] = u[s]; ut[2 * k] = u[s + 1]; fw[2 * k] = 1;
-        uf[2 * k + 1] = u[N - 1 - s]; ut[2 * k + 1] = u[N - 2 - s]; fw[2 * k + 1] = 0;
-        ss[2 * k] = &E.states[pb(k) + s + 1];
-        ss[2 * k + 1] = &E.states[xb(k) + N - 2 - s];
-      }
-      E.step(cs, uf, ut, fw);
-      E.store_many(ss, cs);
-    }
+    run_legs(E, legs, slot);
     E.sync();
     t.stop(long(2 * K) * (N - 1));
-    for (auto* c : cs) E.release(c);
+    for (auto& g : legs) E.release(g.c);
     h->have_psi = h->have_xi = true;
     h->have_xih = false;
     std::vector<int> xs(size_t(K) * N), ys(size_t(K) * N);
@@ -2755,8 +2865,7 @@ int hbm_gradient_multi(hbm_engine* h, int K, const double* U, int N, double* div
     for (int k = 0; k < K; ++k) fx[k] = pb(k) + N - 1;
     auto rf = hbm_pairs(h, fx, fy, false);
     for (int k = 0; k < K; ++k) { F[2 * k] = rf[k].real(); F[2 * k + 1] = rf[k].imag(); }
-    shrink.ok = true;
-    E.shrink_states(keep);  // a device failure here is this call's status
+    heap.done();
   });
 }
 
@@ -2780,21 +2889,7 @@ int hbm_xi_dH(hbm_engine* h) {
     const int B = hbm_batch(h, N);
     E.reserve_chains(std::max(E.nchain_cap, B), false);
     Timer t(h, 2);
-    for (int t0 = 0; t0 < N; t0 += B) {
-      const int nb = std::min(B, N - t0);
-      std::vector<View> in;
-      std::vector<Chain*> out;
-      std::vector<State*> ss;
-      for (int i = 0; i < nb; ++i) {
-        in.push_back(E.states[h->xi_base() + t0 + i].view());
-        out.push_back(E.acquire(false));
-        ss.push_back(&E.states[h->xih_base() + t0 + i]);
-      }
-      E.apply_dH(in, out);
-      E.store_many(ss, out);
-      E.sync();
-      for (auto* c : out) E.release(c);
-    }
+    dH_slots(E, E.states, h->xi_base(), h->xih_base(), N, B);
     t.stop();
     h->have_xih = true;
   });
@@ -2820,55 +2915,34 @@ int hbm_hessian_rows(hbm_engine* h, const double* u, int N, const int* rows, int
     for (int r0 = 0; r0 < nrows; r0 += B) {
       const int nb = std::min(B, nrows - r0);
       std::vector<int> ri(rs.begin() + r0, rs.begin() + r0 + nb);
-      std::vector<Chain*> cs(nb);
+      std::vector<Chain*> cs;
       std::vector<View> in(nb);
-      for (int k = 0; k < nb; ++k) { cs[k] = E.acquire(false); in[k] = E.states[h->psi_base() + ri[k]].view(); }
-      E.apply_dH(in, cs);
-      std::vector<View> vs;
-      for (auto* c : cs) vs.push_back(c->view());
-      const std::vector<double> n2 = E.site_norm2(vs, 1);
-      std::vector<double> nrm(nb);
-      for (int k = 0; k < nb; ++k) nrm[k] = std::sqrt(std::max(0.0, n2[k]));
+      for (int k = 0; k < nb; ++k) in[k] = E.states[h->psi_base() + ri[k]].view();
+      const std::vector<double> nrm = join_rows(E, in, cs);
       // diagonal (:259-264)
       {
         std::vector<View> xs;
         for (int k = 0; k < nb; ++k) xs.push_back(E.states[h->xih_base() + ri[k]].view());
-        auto ov = E.overlaps(xs, vs, false);
-        for (int k = 0; k < nb; ++k) {
-          const int i = ri[k];
-          const double v1 = (Fc * ov[k]).real(), v2 = -std::norm(dv(i));
-          H[size_t(i) * N + i] = dt2 * (v1 + v2);
-        }
+        auto ov = E.overlaps(xs, views_of(cs), false);
+        for (int k = 0; k < nb; ++k) H[size_t(ri[k]) * N + ri[k]] = hess_diag(dt2, Fc, ov[k], dv(ri[k]));
       }
-      // off-diagonal (:266-278): lockstep over s
-      std::vector<int> act(nb);
-      for (int k = 0; k < nb; ++k) act[k] = k;
-      for (int s = 1;; ++s) {
-        std::vector<Chain*> a;
-        std::vector<int> ak;
-        for (int k : act)
-          if (ri[k] + s <= N - 2) { a.push_back(cs[k]); ak.push_back(k); }
-        if (a.empty()) break;
-        std::vector<double> uf(a.size()), ut(a.size());
-        std::vector<int> fw(a.size(), 1);
-        for (size_t m = 0; m < a.size(); ++m) { const int j = ri[ak[m]] + s; uf[m] = u[j - 1]; ut[m] = u[j]; }
-        E.step(a, uf, ut, fw);
-        nsteps += long(a.size());
+      // off-diagonal (:266-278): row i is a leg from i to N-2, all in lockstep
+      std::vector<Leg> legs;
+      for (int k = 0; k < nb; ++k) legs.push_back({cs[k], u, ri[k], N - 2, true});
+      for (;;) {
+        const std::vector<int> moved = step_legs(E, legs);
+        if (moved.empty()) break;
+        nsteps += long(moved.size());
         std::vector<View> xs, ys;
-        for (size_t m = 0; m < a.size(); ++m) {
-          xs.push_back(E.states[h->xih_base() + ri[ak[m]] + s].view());
-          ys.push_back(a[m]->view());
+        for (int k : moved) {
+          xs.push_back(E.states[h->xih_base() + legs[k].t].view());
+          ys.push_back(cs[k]->view());
         }
         auto ov = E.overlaps(xs, ys, false);
-        for (size_t m = 0; m < a.size(); ++m) {
-          const int k = ak[m], i = ri[k], j = i + s;
-          const double v1 = (Fc * ov[m] * nrm[k]).real();
-          const double v2 = -(dv(i) * std::conj(dv(j))).real();
-          const double r = dt2 * (v1 + v2);
-          H[size_t(i) * N + j] = r;
-          H[size_t(j) * N + i] = r;
+        for (size_t m = 0; m < moved.size(); ++m) {
+          const int k = moved[m], i = ri[k], j = legs[k].t;
+          hess_set(H, N, i, j, hess_offdiag(dt2, Fc, ov[m], nrm[k], dv(i), dv(j)));
         }
-        act = ak;
       }
       for (auto* c : cs) E.release(c);
     }
@@ -2882,7 +2956,7 @@ int hbm_hessian_rows(hbm_engine* h, const double* u, int N, const int* rows, int
 static double heap_growth_bytes(const hbm_engine* h, double slots) {
   return slots <= double(h->E->heap_slots) ? 0.0 : 16.0 * double(h->E->state_cap) * slots;
 }
-double hbm_traj_bytes(const hbm_engine* h, int N) { return heap_growth_bytes(h, 3.0 * N + 6.0); }
+double hbm_traj_bytes(const hbm_engine* h, int N) { return heap_growth_bytes(h, double(h->traj_slots(N))); }
 // bytes a pool of n chains would newly allocate on an engine holding `have`
 // chains (the pool itself, 16 B per element, and half as much again for the
 // workspace arenas the chains' launches draw on); a call that still runs out
@@ -2892,7 +2966,8 @@ static double chain_growth_bytes(const hbm::Engine& E, int n, int have, bool wid
 }
 double hbm_gradient_multi_bytes(const hbm_engine* h, int K, int N) {
   const hbm::Engine& E = *h->E;
-  return heap_growth_bytes(h, 3.0 * N + 6.0 + 2.0 * N * (K - 1)) + chain_growth_bytes(E, 2 * K, E.nchain_cap, false);
+  return heap_growth_bytes(h, double(h->traj_slots(N)) + 2.0 * N * (K - 1)) +
+         chain_growth_bytes(E, 2 * K, E.nchain_cap, false);
 }
 
 // Checkpointed getHessian (see hbm.hpp).  Time-major row sweep: all rows of a
@@ -2922,7 +2997,7 @@ int hbm_hessian_ckpt(hbm_engine* h, const double* u, int N, const int* rows, int
     // every checkpoint stored on the way) when N half-trajectory slots fit, so the
     // row passes recompute only the segments their rows need; else the
     // checkpoint-only pass and divT in the first row pass
-    HeapRestore heap(E);  // checkpoints, half trajectories and segments are not kept
+    GiveBack heap(h, E.heap_slots);  // checkpoints, half trajectories and segments are not kept
     bool mid = false;
     if (const char* e = std::getenv("OCG_HBM_CKPT_MID")) mid = std::atoi(e) != 0;
     else {
@@ -2952,80 +3027,17 @@ int hbm_hessian_ckpt(hbm_engine* h, const double* u, int N, const int* rows, int
     E.reserve_chains(std::max(E.nchain_cap, 2), false);
     auto ckpt_psi = [&](int t) { return (t == N - 1 || t % K == 0) ? ckp + (t == N - 1 ? S : t / K) : -1; };
     auto ckpt_xi = [&](int t) { return (t == N - 1 || t % K == 0) ? ckx + (t == N - 1 ? S : t / K) : -1; };
+    auto ckpt = [&](int leg, int t) { return leg == 0 ? ckpt_psi(t) : ckpt_xi(t); };
     if (mid) {
-      const int tm = (N - 1) / 2;
       auto half = [&](int t) { return R + t; };  // psi_t for t <= tm, xi_t above
-      Chain* cp = E.acquire(false);
-      Chain* cx = E.acquire(false);
-      std::vector<Chain*> both{cp, cx};
-      E.load_many(both, {E.states[0].view(), E.states[1].view()});
-      E.store_many({&E.states[half(0)], &E.states[ckp], &E.states[half(N - 1)], &E.states[ckx + S]}, {cp, cp, cx, cx});
-      auto advance = [&](int& tp, int pe, int& tx, int xe) {
-        std::vector<Chain*> c;
-        std::vector<double> uf, ut;
-        std::vector<int> fw;
-        if (tp < pe) { c.push_back(cp); uf.push_back(u[tp]); ut.push_back(u[tp + 1]); fw.push_back(1); }
-        if (tx > xe) { c.push_back(cx); uf.push_back(u[tx]); ut.push_back(u[tx - 1]); fw.push_back(0); }
-        E.step(c, uf, ut, fw);
-        if (tp < pe) ++tp;
-        if (tx > xe) --tx;
-      };
-      int tp = 0, tx = N - 1;
-      while (tp < tm || tx > tm + 1) {  // phase 1: both halves stored, checkpoints on the way
-        const bool mp = tp < tm, mx = tx > tm + 1;
-        advance(tp, tm, tx, tm + 1);
-        std::vector<State*> ss;
-        std::vector<Chain*> cc;
-        if (mp) {
-          ss.push_back(&E.states[half(tp)]); cc.push_back(cp);
-          if (ckpt_psi(tp) >= 0) { ss.push_back(&E.states[ckpt_psi(tp)]); cc.push_back(cp); }
-        }
-        if (mx) {
-          ss.push_back(&E.states[half(tx)]); cc.push_back(cx);
-          if (ckpt_xi(tx) >= 0) { ss.push_back(&E.states[ckpt_xi(tx)]); cc.push_back(cx); }
-        }
-        E.store_many(ss, cc);
-      }
-      while (tp < N - 1 || tx > 0) {  // phase 2: each new state paired with the stored other half
-        const bool mp = tp < N - 1, mx = tx > 0;
-        advance(tp, N - 1, tx, 0);
-        std::vector<State*> ss;
-        std::vector<Chain*> cc;
-        if (mp && ckpt_psi(tp) >= 0) { ss.push_back(&E.states[ckpt_psi(tp)]); cc.push_back(cp); }
-        if (mx && ckpt_xi(tx) >= 0) { ss.push_back(&E.states[ckpt_xi(tx)]); cc.push_back(cx); }
-        if (!ss.empty()) E.store_many(ss, cc);
-        std::vector<View> xs, ys;  // divT_t = overlapC(xi_t, dH, psi_t) (:409-419)
-        if (mp) { xs.push_back(E.states[half(tp)].view()); ys.push_back(cp->view()); }
-        if (mx) { xs.push_back(cx->view()); ys.push_back(E.states[half(tx)].view()); }
-        const auto r = E.overlaps(xs, ys, true);
-        int k = 0;
-        if (mp) dv[tp] = r[k++];
-        if (mx) dv[tx] = r[k++];
-      }
-      Fc = E.overlaps({cp->view()}, {E.states[1].view()}, false)[0];  // F = overlapC(psi_{N-1}, target) (:242)
-      E.sync();
-      E.release(cp);
-      E.release(cx);
+      meet_in_the_middle(E, u, N, half, ckpt_psi, ckpt_xi, dv, Fc);
     } else {
       // 1. psi forward / xi backward in one batch, checkpoints only
-      std::vector<Chain*> cs{E.acquire(false), E.acquire(false)};
-      E.load_many(cs, {E.states[0].view(), E.states[1].view()});
-      E.store_many({&E.states[ckp], &E.states[ckx + S]}, cs);
-      std::vector<double> uf(2), ut(2);
-      std::vector<int> fw{1, 0};
-      for (int s = 0; s + 1 < N; ++s) {
-        uf[0] = u[s]; ut[0] = u[s + 1];
-        uf[1] = u[N - 1 - s]; ut[1] = u[N - 2 - s];
-        E.step(cs, uf, ut, fw);
-        const int tp = s + 1, tx = N - 2 - s;
-        std::vector<State*> ss;
-        std::vector<Chain*> cc;
-        if (ckpt_psi(tp) >= 0) { ss.push_back(&E.states[ckpt_psi(tp)]); cc.push_back(cs[0]); }
-        if (tx % K == 0) { ss.push_back(&E.states[ckx + tx / K]); cc.push_back(cs[1]); }
-        if (!ss.empty()) E.store_many(ss, cc);
-      }
+      std::vector<Leg> legs{{E.acquire(false), u, 0, N - 1, true}, {E.acquire(false), u, N - 1, 0, false}};
+      start_legs(E, E.states, legs, {E.states[0].view(), E.states[1].view()}, ckpt);
+      run_legs(E, legs, ckpt);
       E.sync();
-      for (auto* c : cs) E.release(c);
+      for (auto& g : legs) E.release(g.c);
       // F = overlapC(psi_{N-1}, target) (:242)
       Fc = E.overlaps({E.states[ckp + S].view()}, {E.states[1].view()}, false)[0];
     }
@@ -3055,19 +3067,12 @@ int hbm_hessian_ckpt(hbm_engine* h, const double* u, int N, const int* rows, int
         // batch of two chains (every HBM-engine kernel is batch-independent: the
         // same states as two single-chain passes, in half the dependent steps)
         {
-          std::vector<Chain*> c2{E.acquire(false), E.acquire(false)};
-          E.load_many(c2, {E.states[ckp + s].view(), E.states[ckx + s + 1].view()});
-          E.store_many({&E.states[sgp], &E.states[sgx + b - a]}, c2);
-          std::vector<double> uf(2), ut(2);
-          const std::vector<int> fw{1, 0};
-          for (int m = 0; m < b - a; ++m) {
-            uf[0] = u[a + m]; ut[0] = u[a + m + 1];
-            uf[1] = u[b - m]; ut[1] = u[b - m - 1];
-            E.step(c2, uf, ut, fw);
-            E.store_many({&E.states[sgp + m + 1], &E.states[sgx + b - m - 1 - a]}, c2);
-          }
+          std::vector<Leg> legs{{E.acquire(false), u, a, b, true}, {E.acquire(false), u, b, a, false}};
+          auto seg = [&](int leg, int t) { return (leg == 0 ? sgp : sgx) + t - a; };
+          start_legs(E, E.states, legs, {E.states[ckp + s].view(), E.states[ckx + s + 1].view()}, seg);
+          run_legs(E, legs, seg);
           E.sync();
-          for (auto* c : c2) E.release(c);
+          for (auto& g : legs) E.release(g.c);
         }
         // divT_t = overlapC(xi_t, dH, psi_t) (:409-419), t in [a, b) (and N-1 at the end)
         if (first) {
@@ -3080,56 +3085,32 @@ int hbm_hessian_ckpt(hbm_engine* h, const double* u, int N, const int* rows, int
         if (!need_rows) continue;
         // xiH_j = exactApplyMPO(dH, xi_j) for the rows' times in this segment (:300-303)
         const int j0 = std::max(a, imin), j1 = std::min(b - 1, N - 2);
-        {
-          std::vector<View> in;
-          std::vector<Chain*> out;
-          std::vector<State*> ss;
-          for (int j = j0; j <= j1; ++j) {
-            in.push_back(E.states[sgx + j - a].view());
-            out.push_back(E.acquire(false));
-            ss.push_back(&E.states[sgh + j - a]);
-          }
-          E.apply_dH(in, out);
-          E.store_many(ss, out);
-          E.sync();
-          for (auto* c : out) E.release(c);
-        }
+        dH_slots(E, E.states, sgx + j0 - a, sgh + j0 - a, j1 - j0 + 1, j1 - j0 + 1);
         for (int j = j0; j <= j1; ++j) {
           // active rows: step u[j-1] -> u[j] (timeStepper.step(psiH, ..), :269), overlap with xiH_j
           if (!act.empty()) {
             E.step(act, std::vector<double>(act.size(), u[j - 1]), std::vector<double>(act.size(), u[j]),
                    std::vector<int>(act.size(), 1));
-            std::vector<View> xs(act.size(), E.states[sgh + j - a].view()), ys;
-            for (auto* c : act) ys.push_back(c->view());
-            const auto ov = E.overlaps(xs, ys, false);
-            for (size_t m = 0; m < act.size(); ++m) {
-              const int i = ai[m];
-              const double v1 = (Fc * ov[m] * nrm[m]).real();
-              const double v2 = -(dv[i] * std::conj(dv[j])).real();
-              const double r = dt2 * (v1 + v2);
-              H[size_t(i) * N + j] = r;
-              H[size_t(j) * N + i] = r;
-            }
+            const std::vector<View> xs(act.size(), E.states[sgh + j - a].view());
+            const auto ov = E.overlaps(xs, views_of(act), false);
+            for (size_t m = 0; m < act.size(); ++m)
+              hess_set(H, N, ai[m], j, hess_offdiag(dt2, Fc, ov[m], nrm[m], dv[ai[m]], dv[j]));
           }
           // rows joining at j: psiH_i = dH psi_i, normiH, diagonal (:256-264)
           std::vector<int> join;
           while (next < r0 + nb && rs[next] == j) join.push_back(rs[next++]);
           if (!join.empty()) {
-            std::vector<View> in(join.size(), E.states[sgp + j - a].view());
+            const std::vector<View> in(join.size(), E.states[sgp + j - a].view());
             std::vector<Chain*> cs;
-            for (size_t m = 0; m < join.size(); ++m) cs.push_back(E.acquire(false));
-            E.apply_dH(in, cs);
-            std::vector<View> vs;
-            for (auto* c : cs) vs.push_back(c->view());
-            const std::vector<double> n2 = E.site_norm2(vs, 1);
-            std::vector<View> xs(join.size(), E.states[sgh + j - a].view());
-            const auto ov = E.overlaps(xs, vs, false);
+            const std::vector<double> n = join_rows(E, in, cs);
+            const std::vector<View> xs(join.size(), E.states[sgh + j - a].view());
+            const auto ov = E.overlaps(xs, views_of(cs), false);
             for (size_t m = 0; m < join.size(); ++m) {
               const int i = join[m];
-              H[size_t(i) * N + i] = dt2 * ((Fc * ov[m]).real() - std::norm(dv[i]));
+              H[size_t(i) * N + i] = hess_diag(dt2, Fc, ov[m], dv[i]);
               act.push_back(cs[m]);
               ai.push_back(i);
-              nrm.push_back(std::sqrt(std::max(0.0, n2[m])));
+              nrm.push_back(n[m]);
             }
           }
         }
@@ -3432,7 +3413,7 @@ int hbm_ground_state(hbm_engine* h, const int* dims, const double* data, double 
   const int rc = guard(h, [&] {
     hbm::Engine& E = *h->E;
     E.set_caps(widest_of(E, dims));
-    E.reserve_states(size_t(h->xih_base() + h->N + 2));
+    E.reserve_states(size_t(h->traj_slots(h->N)));
     const int prev = h->xih_base() + h->N;  // scratch slot after the trajectories
     E.upload_state(E.states[prev], dims, data);
     E.reserve_chains(std::max(E.nchain_cap, 1), false);
@@ -3516,7 +3497,7 @@ bool pipe_debug() {
     }                                           \
   } while (0)
 // first slot of the row states and the slots the pipeline needs in total
-int pipe_psih_base(const hbm_engine* h, int N) { return 4 + 3 * N + 2; }
+int pipe_psih_base(const hbm_engine* h, int N) { return int(h->traj_slots(N)); }
 }  // namespace
 
 double hbm_pipe_bytes(const hbm_engine* h, int N, const int* rows, int nrows) {
@@ -3547,32 +3528,9 @@ int hbm_hessian_pipe(hbm_engine* h, const double* u, int N, const int* rows, int
     std::vector<int> rsoff(nrows + 1);
     rsoff[0] = psih0 + N;
     for (int k = 0; k < nrows; ++k) rsoff[k + 1] = rsoff[k] + (N - 2 - rs[k]);
-    // a failed call gives back everything it grew — its row-state slots, the
-    // context engine's chain pool, the two worker engines with their pools and
-    // arenas — so that the two-phase path ocg_hessian may retry after an
-    // allocation failure sees that memory free
-    struct ShrinkOnError {
-      hbm_engine* h;
-      size_t keep;
-      int chains0;
-      bool ok = false;
-      ~ShrinkOnError() {
-        if (ok) return;
-        hbm::Engine& E = *h->E;
-        try {
-          E.drain();
-          for (auto& W : h->W)
-            if (W) {
-              W->drain();
-              W.reset();
-            }
-          E.release_all();
-          E.shrink_chains(chains0);
-          E.shrink_states(keep);
-        } catch (...) {
-        }
-      }
-    } undo{h, std::max(E.heap_slots, size_t(h->xih_base() + N + 2)), E.nchain_cap};
+    // a failed call gives back everything it grew: its row-state slots, the context
+    // engine's chain pool and the two worker engines
+    GiveBack undo(h, std::max(E.heap_slots, size_t(h->traj_slots(N))), true);
     E.reserve_states(size_t(rsoff[nrows]));
     hbm::Engine& WH = pipe_worker(h, 0);
     hbm::Engine& WX = pipe_worker(h, 1);
@@ -3595,33 +3553,20 @@ int hbm_hessian_pipe(hbm_engine* h, const double* u, int N, const int* rows, int
         hbm::Engine& W = WX;
         W.reserve_chains(std::max(W.nchain_cap, B), false);
         {
-          std::vector<Chain*> c1{W.acquire(false)};
-          W.load_many(c1, {E.states[1].view()});
-          W.store_many({&E.states[h->xi_base() + N - 1]}, c1);
-          for (int s = 0; s + 1 < N && !abort_.load(); ++s) {
-            W.step(c1, {u[N - 1 - s]}, {u[N - 2 - s]}, {0});
-            W.store_many({&E.states[h->xi_base() + N - 2 - s]}, c1);
-            PIPE_LOG("[pipe X] xi step %d\n", s);
+          std::vector<Leg> legs{{W.acquire(false), u, N - 1, 0, false}};
+          auto slot = [&](int, int t) { return h->xi_base() + t; };
+          start_legs(W, E.states, legs, {E.states[1].view()}, slot);
+          while (!abort_.load()) {
+            const std::vector<int> moved = step_legs(W, legs);
+            if (moved.empty()) break;
+            store_legs(W, E.states, legs, moved, slot);
+            PIPE_LOG("[pipe X] xi step %d\n", N - 2 - legs[0].t);
           }
           W.sync();
-          W.release(c1[0]);
+          W.release(legs[0].c);
         }
         PIPE_LOG("[pipe X] xi done, xiH in batches of %d\n", B);
-        for (int t0 = 0; t0 < N && !abort_.load(); t0 += B) {
-          const int nb = std::min(B, N - t0);
-          std::vector<View> in;
-          std::vector<Chain*> out;
-          std::vector<State*> ss;
-          for (int i = 0; i < nb; ++i) {
-            in.push_back(E.states[h->xi_base() + t0 + i].view());
-            out.push_back(W.acquire(false));
-            ss.push_back(&E.states[h->xih_base() + t0 + i]);
-          }
-          W.apply_dH(in, out);
-          W.store_many(ss, out);
-          W.sync();
-          for (auto* c : out) W.release(c);
-        }
+        dH_slots(W, E.states, h->xi_base(), h->xih_base(), N, B, &abort_);
       } catch (...) {
         ex[1] = std::current_exception();
         abort_.store(1);
@@ -3646,14 +3591,10 @@ int hbm_hessian_pipe(hbm_engine* h, const double* u, int N, const int* rows, int
           std::vector<State*> ss;
           for (int k = next; k < end; ++k) {
             in.push_back(E.states[h->psi_base() + rs[k]].view());
-            out.push_back(W.acquire(false));
             ss.push_back(&E.states[psih0 + k]);
           }
-          W.apply_dH(in, out);
-          std::vector<View> vs;
-          for (auto* c : out) vs.push_back(c->view());
-          const std::vector<double> n2 = W.site_norm2(vs, 1);
-          for (int k = next; k < end; ++k) nrm[k] = std::sqrt(std::max(0.0, n2[k - next]));
+          const std::vector<double> n = join_rows(W, in, out);
+          std::copy(n.begin(), n.end(), nrm.begin() + next);
           W.store_many(ss, out);
           W.sync();
           for (auto* c : out) W.release(c);
@@ -3789,16 +3730,11 @@ int hbm_hessian_pipe(hbm_engine* h, const double* u, int N, const int* rows, int
     size_t e = 0;
     for (int k = 0; k < nrows; ++k) {
       const int i = rs[k];
-      H[size_t(i) * N + i] = dt2 * ((Fh * ov[e++]).real() - std::norm(dv(i)));  // (:259-264)
-      for (int j = i + 1; j <= N - 2; ++j) {                                     // (:266-278)
-        const double v1 = (Fh * ov[e++] * nrm[k]).real();
-        const double v2 = -(dv(i) * std::conj(dv(j))).real();
-        const double r = dt2 * (v1 + v2);
-        H[size_t(i) * N + j] = r;
-        H[size_t(j) * N + i] = r;
-      }
+      H[size_t(i) * N + i] = hess_diag(dt2, Fh, ov[e++], dv(i));
+      for (int j = i + 1; j <= N - 2; ++j)
+        hess_set(H, N, i, j, hess_offdiag(dt2, Fh, ov[e++], nrm[k], dv(i), dv(j)));
     }
     tall.stop(long(N - 1) * 2 + long(rsoff[nrows] - rsoff[0]));
-    undo.ok = true;
+    undo.kept();
   });
 }
