@@ -81,8 +81,9 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * Changelog: 2 ocg_info.fast_chain (round 5), OCG_ENOMEM returned by
  * ocg_hessian when OCG_HBM_PIPE=1 forces a pipeline that cannot allocate;
  * 3 ocg_get_info_sz, ocg_get_path_stats, ocg_abi_version (round 6);
- * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9. */
-#define OCG_ABI_VERSION 4
+ * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9;
+ * 5 ocg_observe_spectrum, ocg_observe_spectrum_states. */
+#define OCG_ABI_VERSION 5
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
 int ocg_set_tstep(ocg_ctx* ctx, double tstep);
@@ -239,6 +240,37 @@ int ocg_observe(ocg_ctx* ctx, int which, const int* ts, int nt, const int* rows,
 int ocg_observe_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, const int* rows, int nrows,
                        double* norm2, double* occ, int* bond, double* corr_ada, double* corr_nn);
 
+/* Entanglement (Schmidt) spectra and entropies of the device-resident
+ * trajectory states at every bond b = 1..L-1 (between sites b and b+1):
+ * AnalyzeQuench's entanglementEntropy(sites, psi) (include/correlations.hpp:
+ * 119-149) evaluated where the states are.  which, ts and the existence rules
+ * are those of ocg_observe.  With Lenv / Renv the environments of ocg_observe
+ * (Lenv_k[q'] = sum A^H Lenv_{k-1} A, Renv_{k-1}[q] = sum A Renv_k A^H) the
+ * weights of bond b in sector q (left particle count) are the eigenvalues of
+ * X = S^H Renv_b[q] S, S = V diag(sqrt(max(lambda, 0))), Lenv_b[q] = V
+ * diag(lambda) V^H: gauge-free, raw (their sum over a bond is norm2).  A
+ * sector of dims without an Lenv or Renv block contributes dims[b][q] zero
+ * weights, so a bond always has bond[b] weights.
+ * Outputs (NULL: skipped):
+ *   entropy[nt][L-1]        S_b = -sum_{p > 1e-12} p ln p over p = max(w, 0) /
+ *                           sum max(w, 0) (natural log; 0 for a zero state)
+ *   schmidt[nt][L-1][wcap]  the weights of the bond, descending, ties by sector
+ *                           ascending; entries past the bond dimension are 0
+ *   sector[nt][L-1][wcap]   the sector q of each weight; -1 past the bond dimension
+ * wcap below a requested state's largest bond dimension: OCG_ECAP when schmidt
+ * or sector is wanted (ignored otherwise).  Bond sectors of order up to 512
+ * (OCG_ECAP above); OCG_ENUM if a Jacobi eigen block does not converge.
+ * Chunked as ocg_observe; a state's results are bit-identical whatever else is
+ * requested with it.  Only results leave the device (the weights only when
+ * asked for).  Reads the trajectories only. */
+int ocg_observe_spectrum(ocg_ctx* ctx, int which, const int* ts, int nt, int wcap, double* entropy,
+                         double* schmidt, int* sector);
+/* The same for n caller-supplied host states (as ocg_observe_states: any gauge
+ * or norm; a sector may be larger than its Schmidt-rank bound), staged on the
+ * device in batches. */
+int ocg_observe_spectrum_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, int wcap,
+                                double* entropy, double* schmidt, int* sector);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -273,7 +305,7 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * OCG_HBM_PIPE=1, which makes any pipeline failure the call's status),
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
  * segment length of the last one), 9 the observable kernels of ocg_observe /
- * ocg_observe_states (HIP-event time of their chunks, kernel launches, and the
+ * ocg_observe_states / ocg_observe_spectrum[_states] (HIP-event time of their chunks, kernel launches, and the
  * algorithmic bytes and flops of the host-built task lists).  Sums since the
  * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,

@@ -3174,6 +3174,29 @@ struct ObsBackend {
     t.clear();
     p.clear();
   }
+  int eig(std::vector<obs::ETask>& t, int* status) {
+    std::vector<obs::ETask> g[2];
+    obs::eig_split(t, g[0], g[1]);
+    int launches = 0;
+    size_t done = 0;
+    for (int i = 0; i < 2; ++i) {
+      if (g[i].empty()) continue;
+      ++launches;
+      HCK(obs::eig_launch(g[i], status + done, i == 0 ? 64 : 256, E.st,
+                          [&](std::vector<obs::ETask>& v) { return E.upload(v); }));
+      done += g[i].size();
+    }
+    t.clear();
+    return launches;
+  }
+  void entropy(std::vector<obs::STask>& t, double* out) {
+    if (!t.empty()) {
+      const obs::STask* dt = E.upload(t);
+      hipLaunchKernelGGL(obs::k_obs_entropy, dim3(unsigned(t.size())), dim3(64), 0, E.st, dt, out);
+      HCK(hipGetLastError());
+    }
+    t.clear();
+  }
 };
 
 obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
@@ -3196,8 +3219,11 @@ obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
 
 // the observables of state slots[i] into entry out0 + i of the outputs, in
 // chunks whose workspace fits half the free HBM
+void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
+                   double* occ_buf, const obs::SpecOutputs* so);
+// with so the spectrum stages run too and their results go to *so
 void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                   double* occ_buf) {
+                   double* occ_buf, const obs::SpecOutputs* so = nullptr) {
   hbm::Engine& E = *h->E;
   const int L = E.L, nst = int(slots.size());
   std::vector<obs::StateDesc> desc(nst);
@@ -3206,8 +3232,25 @@ void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, co
     if (bond)
       for (int b = 0; b <= L; ++b) bond[(out0 + i) * (L + 1) + b] = E.states[slots[i]].dims.bond(b);
   }
-  const obs::Want want = obs::want_of(o);
-  if (!want.norm && !want.env()) return;
+  observe_descs(h, desc, out0, o, occ_buf, so);
+}
+
+// the chunks of observe.hpp's driver over states described on the device
+void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
+                   double* occ_buf, const obs::SpecOutputs* so) {
+  hbm::Engine& E = *h->E;
+  const int L = E.L, nst = int(desc.size());
+  obs::Want want = obs::want_of(o);
+  want.spec = so != nullptr;
+  if (!want.norm && !want.env() && !want.spec) return;
+  if (so) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
+    if (so->weights() && so->wcap < wb)
+      throw hbm::Error(2, "wcap " + std::to_string(so->wcap) + " below the largest bond dimension " +
+                              std::to_string(wb));
+    if (wo > obs::kEigMaxOrder) throw hbm::Error(2, "spectrum: a bond sector above order 512");
+  }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
   const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want);
   const size_t budget = obs::chunk_budget();
@@ -3224,12 +3267,31 @@ void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, co
     ObsBackend be{E};
     std::vector<obs::Dest> dests;
     Timer t(h, 9);
-    const double* d_out = obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr);
+    obs::Spec sp;
+    const double* d_out = obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr);
     std::vector<double> res(2 * std::max<size_t>(dests.size(), 1));
     if (!dests.empty())
       HCK(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost, E.st));
+    std::vector<double> ent, wts;
+    std::vector<int> status;
+    if (so) {  // only results leave the device: the weights when they are asked for
+      ent.resize(std::max<size_t>(S.size() * (L - 1), 1));
+      status.resize(std::max<size_t>(sp.nstatus, 1));
+      wts.resize(so->weights() ? std::max<size_t>(sp.nw, 1) : 0);
+      if (L > 1)
+        HCK(hipMemcpyAsync(ent.data(), sp.d_ent, sizeof(double) * S.size() * (L - 1), hipMemcpyDeviceToHost, E.st));
+      if (sp.nstatus)
+        HCK(hipMemcpyAsync(status.data(), sp.d_status, sizeof(int) * sp.nstatus, hipMemcpyDeviceToHost, E.st));
+      if (so->weights() && sp.nw)
+        HCK(hipMemcpyAsync(wts.data(), sp.d_w, sizeof(double) * sp.nw, hipMemcpyDeviceToHost, E.st));
+    }
     t.stop();
     E.sync();
+    if (so) {
+      for (size_t j = 0; j < sp.nstatus; ++j)
+        if (status[j]) throw hbm::Error(5, "spectrum: a Jacobi eigen block did not converge");
+      obs::scatter_spectrum(sp, S, os, L, E.Q1, ent.data(), wts.data(), *so);
+    }
     obs::scatter(dests, res.data(), o, occ_buf);
     if (o.nrows > 0 && (o.ada || o.nn))
       for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
@@ -3319,6 +3381,75 @@ int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* cons
         E.upload_state(E.states[sb + i], dims + size_t(i0 + i) * nsq, data[i0 + i]);
       }
       observe_slots(h, slots, size_t(i0), o, bond, occ_buf);
+    }
+  });
+}
+
+int hbm_observe_spectrum(hbm_engine* h, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
+                         int* sector) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
+    const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
+    if (!ok) throw hbm::Error(4, "requested trajectory not available");
+    const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
+    std::vector<int> slots(nt);
+    for (int i = 0; i < nt; ++i) {
+      const int t = ts ? ts[i] : i;
+      if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
+      slots[i] = base + t;
+    }
+    if (nt == 0 || (!entropy && !schmidt && !sector)) return;
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
+    observe_slots(h, slots, 0, o, nullptr, nullptr, &so);
+  });
+}
+
+int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const double* const* data, int wcap,
+                                double* entropy, double* schmidt, int* sector) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
+    if (n == 0 || (!entropy && !schmidt && !sector)) return;
+    const int nsq = (E.L + 1) * E.Q1;
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
+    for (int i = 0; i < n; ++i) {  // before anything is written
+      const int* d = dims + size_t(i) * nsq;
+      for (int j = 0; j < nsq; ++j)
+        if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
+      for (int q = 0; q < E.Q1; ++q)
+        if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
+          throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
+      for (int b = 1; b < E.L && so.weights(); ++b) {
+        long sum = 0;
+        for (int q = 0; q < E.Q1; ++q) sum += d[size_t(b) * E.Q1 + q];
+        if (sum > wcap) throw hbm::Error(2, "wcap below the largest bond dimension of the states");
+      }
+    }
+    // Staged a batch at a time in the compact interchange format itself: its blocks are
+    // the contiguous row-major matrices the descriptors want, and a sector may be larger
+    // than the Hilbert-space bound of the state slots (a padded or over-parametrised state).
+    const int B = std::min(n, 64);
+    for (int i0 = 0; i0 < n; i0 += B) {
+      const int nb = std::min(B, n - i0);
+      std::vector<size_t> at(nb + 1, 0);
+      for (int i = 0; i < nb; ++i) {
+        obs::StateDesc tmp;
+        at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, nullptr, tmp);
+      }
+      hbm::DBuf<double> stage;
+      stage.reserve(2 * std::max<size_t>(at[nb], 1));
+      std::vector<obs::StateDesc> desc(nb);
+      for (int i = 0; i < nb; ++i) {
+        if (at[i + 1] > at[i])
+          HCK(hipMemcpyAsync(stage.p + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
+                             E.st));
+        obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, stage.p + 2 * at[i], desc[i]);
+      }
+      observe_descs(h, desc, size_t(i0), o, nullptr, &so);
+      E.sync();
     }
   });
 }

@@ -64,6 +64,11 @@ int hbm_observe(hbm_engine* h, int which, const int* ts, int nt, const int* rows
                 double* occ, int* bond, double* ada, double* nn);
 int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* const* data, const int* rows, int nrows,
                        double* norm2, double* occ, int* bond, double* ada, double* nn);
+// ocg_observe_spectrum / ocg_observe_spectrum_states (observe.hpp's spectrum stages, observe_eig.hpp's kernels)
+int hbm_observe_spectrum(hbm_engine* h, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
+                         int* sector);
+int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const double* const* data, int wcap,
+                                double* entropy, double* schmidt, int* sector);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM
 // kernel (k_gemm) with its algorithmic bytes and flops; 9: the observable kernels
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps);

@@ -13,6 +13,10 @@
 // A·Renv^H, the new environments sum_n A^H·(E·A), and the closes
 // sum conj(X)∘Y.  Every dependency is a kernel boundary on one stream.
 //
+// With a Spec the spectrum stages follow the sweeps (ocg_observe_spectrum):
+// the Schmidt weights and entropies of every bond from Lenv_b and Renv_b on
+// observe_eig.hpp's batched Jacobi eigensolver (see run_chunk).
+//
 // Determinism: an output element is computed by one wave (GEMM tile) or one
 // workgroup (close) from that state's operands alone, in an order fixed by the
 // block shapes: results do not depend on what else is in the chunk.
@@ -20,12 +24,16 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <utility>
 #include <vector>
+
+#include "observe_eig.hpp"
 
 namespace obs {
 
@@ -65,7 +73,16 @@ struct CTask {
 
 struct Want {
   bool norm = false, occ = false, ada = false, nn = false;
+  bool spec = false;  // Schmidt weights and entropies of every bond (run_chunk's Spec argument)
   bool env() const { return occ || ada || nn; }
+};
+// the spectrum results of one chunk (device addresses, valid until the chunk's sync)
+struct Spec {
+  double* d_ent = nullptr;   // [state][L-1] entropies
+  double* d_w = nullptr;     // per state and bond b = 1..L-1 its bond[b] weights, sector after sector
+  int* d_status = nullptr;   // one word per eigen block, nonzero: not converged
+  size_t nw = 0, nstatus = 0;
+  std::vector<size_t> woff;  // [state * (L-1) + b-1]: where bond b's weights start in d_w
 };
 // where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn
 struct Dest {
@@ -180,6 +197,8 @@ __global__ __launch_bounds__(kCloseNT) void k_obs_close(const CTask* __restrict_
 //   const double* one()                   a device complex 1
 //   void gemm(std::vector<Task>&, std::vector<Seg>&)
 //   void close(std::vector<CTask>&, std::vector<Pair>&, double* out)
+//   int eig(std::vector<ETask>&, int* status)     one eigen stage; returns its launches
+//   void entropy(std::vector<STask>&, double* out)
 
 // dry run: the workspace a chunk would take (256-byte granules, as the arenas)
 struct CountBackend {
@@ -201,6 +220,18 @@ struct CountBackend {
     bytes += al(sizeof(CTask) * t.size()) + al(sizeof(Pair) * p.size());
     t.clear();
     p.clear();
+  }
+  int eig(std::vector<ETask>& t, int*) {
+    std::vector<ETask> g[2];
+    eig_split(t, g[0], g[1]);
+    for (auto& x : g)
+      if (!x.empty()) bytes += al(sizeof(ETask) * x.size());
+    t.clear();
+    return int(!g[0].empty()) + int(!g[1].empty());
+  }
+  void entropy(std::vector<STask>& t, double*) {
+    bytes += al(sizeof(STask) * t.size());
+    t.clear();
   }
 };
 
@@ -275,6 +306,34 @@ struct RawBackend {
     t.clear();
     p.clear();
   }
+  int eig(std::vector<ETask>& t, int* status) {
+    std::vector<ETask> g[2];
+    eig_split(t, g[0], g[1]);
+    int launches = 0;
+    size_t done = 0;
+    for (int i = 0; i < 2; ++i) {
+      if (g[i].empty()) continue;
+      const size_t cnt = g[i].size();
+      ++launches;
+      if (ok())
+        note(eig_launch(g[i], status ? status + done : nullptr, i == 0 ? 64 : 256, st,
+                        [&](std::vector<ETask>& v) { return upload(v); }));
+      done += cnt;
+    }
+    t.clear();
+    return launches;
+  }
+  void entropy(std::vector<STask>& t, double* out) {
+    if (!t.empty()) {
+      const unsigned ntask = unsigned(t.size());
+      const STask* dt = upload(t);
+      if (ok() && out) {
+        hipLaunchKernelGGL(k_obs_entropy, dim3(ntask), dim3(64), 0, st, dt, out);
+        note(hipGetLastError());
+      }
+    }
+    t.clear();
+  }
 };
 
 // ------------------------------------------------------------------ driver
@@ -286,12 +345,19 @@ inline size_t max_outputs(int L, int p, int nrows, Want w) {
 // Queue every launch of one chunk.  out_slot[i] is state i's index in the
 // caller's outputs; rows are start sites (1..L).  Close task j of the chunk
 // writes complex j of d_out and belongs to dests[j].  Returns d_out.
+// With spec (want.spec) the Lenv of every bond is kept and, after the sweeps,
+// the spectrum stages run over the whole chunk: stage A eigen-decomposes every
+// Lenv_b[q] = V diag(lambda) V^H into S = V diag(sqrt(max(lambda, 0))), two GEMM
+// launches form Y = Renv_b[q] S and X = S^H Y, stage B takes the eigenvalues of
+// X (the Schmidt weights of the sector) and one wave per (state, bond) reduces
+// the entropy.  A sector without an Lenv or Renv block gets zero weights.
 template <class BE>
 double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc*>& S,
                   const std::vector<size_t>& out_slot, const std::vector<int>& rows, Want want,
-                  std::vector<Dest>& dests, Traffic& tr) {
+                  std::vector<Dest>& dests, Traffic& tr, Spec* spec = nullptr) {
   const int Q1 = Q + 1, B = int(S.size()), R = int(rows.size());
   const bool ada = want.ada && R > 0, nn = want.nn && R > 0, env = want.occ || ada || nn;
+  const bool renv = env || spec != nullptr;
   dests.clear();
   double* d_out = be.alloc(size_t(B) * max_outputs(L, p, R, want));
   const double* one = be.one();
@@ -322,7 +388,7 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
 
   // ---- right sweep: Renv[i][b * Q1 + q], b = 1..L
   std::vector<std::vector<const double*>> Renv(B);
-  if (env) {
+  if (renv) {
     for (int i = 0; i < B; ++i) {
       Renv[i].assign(size_t(L + 1) * Q1, nullptr);
       Renv[i][size_t(L) * Q1 + Q] = one;
@@ -368,11 +434,12 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
   struct Open {
     std::vector<const double*> C, N;  // [q] on the current bond (C[s]: d[s+1] x d[s])
   };
-  std::vector<std::vector<const double*>> Lenv(B);
+  std::vector<std::vector<const double*>> Lenv(B), Lall(B);  // Lall[i][b * Q1 + q]: every bond's, for the spectra
   std::vector<std::vector<Open>> open(B, std::vector<Open>(R));
   for (int i = 0; i < B; ++i) {
     Lenv[i].assign(Q1, nullptr);
     Lenv[i][0] = one;
+    if (spec) Lall[i].assign(size_t(L + 1) * Q1, nullptr);
   }
   std::vector<CTask> ct;
   std::vector<Pair> cp;
@@ -519,6 +586,7 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
         // closes below still read the products of the old environments (TC, TN), not these
         open[i][ri] = std::move(nx);
       }
+      if (spec) std::copy(Ln.begin(), Ln.end(), Lall[i].begin() + size_t(k) * Q1);
       Lenv[i] = std::move(Ln);
     }
     launch_gemm();
@@ -574,6 +642,85 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
       be.close(ct, cp, d_out ? d_out + 2 * first : nullptr);
     }
   }
+
+  // ---- spectra of the bonds 1..L-1
+  if (spec) {
+    const int NB = L - 1, lds_max = eig_lds_max();
+    spec->woff.assign(size_t(B) * NB, 0);
+    spec->nw = spec->nstatus = 0;
+    for (int i = 0; i < B; ++i)
+      for (int b = 1; b < L; ++b) {
+        spec->woff[size_t(i) * NB + b - 1] = spec->nw;
+        for (int q = 0; q <= Q; ++q) {
+          const int d = D(i, b, q);
+          spec->nw += size_t(d);
+          if (d > 0) spec->nstatus += (Lall[i][size_t(b) * Q1 + q] && Renv[i][size_t(b) * Q1 + q]) ? 2 : 1;
+        }
+      }
+    // doubles and ints out of the complex-granular workspace
+    spec->d_w = be.alloc((spec->nw + 1) / 2);
+    spec->d_ent = be.alloc((size_t(B) * NB + 1) / 2);
+    spec->d_status = reinterpret_cast<int*>(be.alloc((spec->nstatus + 3) / 4));
+    std::vector<ETask> ea, eb;
+    std::vector<STask> es;
+    auto eig_traffic = [&](const ETask& t) {
+      if (!t.A) return;
+      tr.bytes += 16.0 * t.n * t.n * (t.S ? 2 : 1) + (t.w ? 8.0 * t.n : 0.0);
+      tr.flops += eig_flops(t.n, t.S != nullptr);
+    };
+    struct Sec {
+      const double* r;
+      double *s, *y, *x;
+      int n;
+    };
+    std::vector<Sec> secs;
+    for (int i = 0; i < B; ++i)
+      for (int b = 1; b < L; ++b) {
+        double* w = spec->d_w ? spec->d_w + spec->woff[size_t(i) * NB + b - 1] : nullptr;
+        int nb = 0;
+        for (int q = 0; q <= Q; ++q) {
+          const int d = D(i, b, q);
+          if (d == 0) continue;
+          const double *l = Lall[i][size_t(b) * Q1 + q], *r = Renv[i][size_t(b) * Q1 + q];
+          double* wq = w ? w + nb : nullptr;
+          nb += d;
+          if (!l || !r) {
+            eb.push_back(ETask{nullptr, nullptr, wq, nullptr, d});
+            continue;
+          }
+          const size_t dd = size_t(d) * d;
+          Sec sc{r, be.alloc(dd), be.alloc(dd), be.alloc(dd), d};
+          const size_t wa = eig_work(d, true, lds_max), wb = eig_work(d, false, lds_max);
+          ea.push_back(ETask{l, sc.s, nullptr, wa ? be.alloc(wa) : nullptr, d});
+          eb.push_back(ETask{sc.x, nullptr, wq, wb ? be.alloc(wb) : nullptr, d});
+          secs.push_back(sc);
+        }
+        es.push_back(STask{w, nb});
+      }
+    for (const ETask& t : ea) eig_traffic(t);
+    for (const ETask& t : eb) eig_traffic(t);
+    const size_t na = ea.size();
+    tr.launches += be.eig(ea, spec->d_status);
+    for (const Sec& sc : secs) {
+      const int s0 = int(gs.size());
+      seg(sc.r, sc.n, sc.s, sc.n, sc.n, 0, 1.0);
+      task(sc.y, sc.n, sc.n, s0);
+    }
+    launch_gemm();
+    for (const Sec& sc : secs) {
+      const int s0 = int(gs.size());
+      seg(sc.s, sc.n, sc.y, sc.n, sc.n, 1, 1.0);
+      task(sc.x, sc.n, sc.n, s0);
+    }
+    launch_gemm();
+    tr.launches += be.eig(eb, spec->d_status ? spec->d_status + na : nullptr);
+    if (!es.empty()) {
+      ++tr.launches;
+      tr.bytes += 8.0 * double(spec->nw + es.size());
+      tr.flops += 4.0 * double(spec->nw);
+      be.entropy(es, spec->d_ent);
+    }
+  }
   return d_out;
 }
 
@@ -589,7 +736,8 @@ inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vecto
       CountBackend cb;
       std::vector<Dest> dd;
       Traffic tt;
-      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt);
+      Spec sp;
+      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt, want.spec ? &sp : nullptr);
       it = seen.emplace(desc[i].dims, cb.bytes).first;
     }
     need[i] = it->second;
@@ -661,6 +809,74 @@ inline void diagonals(size_t s, const Outputs& o, const double* occ_buf) {
     }
     if (o.nn) o.nn[at] = n2;
   }
+}
+
+// the descriptor of a state held on the device in the compact interchange format
+// itself (include/ocmps.h: sites 1..L, per site the blocks (q, n) in order, each a
+// contiguous row-major matrix) at d_data; returns its complex elements
+inline size_t compact_desc(int L, int p, int Q, const int* dims, const double* d_data, StateDesc& out) {
+  const int Q1 = Q + 1;
+  out.dims.assign(dims, dims + size_t(L + 1) * Q1);
+  out.blk.assign(size_t(L + 1) * Q1 * p, Blk{});
+  size_t off = 0;
+  for (int k = 1; k <= L; ++k)
+    for (int q = 0; q <= Q; ++q)
+      for (int n = 0; n < p && q + n <= Q; ++n) {
+        const int r = dims[(k - 1) * Q1 + q], c = dims[k * Q1 + q + n];
+        if (r <= 0 || c <= 0) continue;
+        out.blk[(size_t(k) * Q1 + q) * p + n] = Blk{d_data + 2 * off, r, c};
+        off += size_t(r) * c;
+      }
+  return off;
+}
+
+// host outputs of ocg_observe_spectrum (null: not wanted)
+struct SpecOutputs {
+  double* entropy = nullptr;  // [nt][L-1]
+  double* schmidt = nullptr;  // [nt][L-1][wcap]
+  int* sector = nullptr;      // [nt][L-1][wcap]
+  int wcap = 0;
+  bool weights() const { return schmidt || sector; }
+};
+
+// the largest bond dimension and sector order of a state
+inline void widest(const StateDesc& d, int L, int Q1, int& bond, int& order) {
+  for (int b = 1; b < L; ++b) {
+    int sum = 0;
+    for (int q = 0; q < Q1; ++q) {
+      sum += d.dims[size_t(b) * Q1 + q];
+      order = std::max(order, d.dims[size_t(b) * Q1 + q]);
+    }
+    bond = std::max(bond, sum);
+  }
+}
+
+// a chunk's spectrum results (host copies of Spec's buffers; w may be null when
+// no weights are wanted) into the outputs: the weights of a bond descending,
+// ties by sector ascending, padded with 0 / -1 up to wcap
+inline void scatter_spectrum(const Spec& sp, const std::vector<const StateDesc*>& S,
+                             const std::vector<size_t>& out_slot, int L, int Q1, const double* ent,
+                             const double* w, const SpecOutputs& o) {
+  const int NB = L - 1;
+  std::vector<std::pair<double, int>> ws;
+  for (size_t i = 0; i < S.size(); ++i)
+    for (int b = 1; b < L; ++b) {
+      const size_t at = out_slot[i] * NB + (b - 1);
+      if (o.entropy) o.entropy[at] = ent[i * NB + (b - 1)];
+      if (!o.weights()) continue;
+      ws.clear();
+      const double* wb = w + sp.woff[i * NB + (b - 1)];
+      for (int q = 0; q < Q1; ++q)
+        for (int j = 0; j < S[i]->dims[size_t(b) * Q1 + q]; ++j) ws.emplace_back(*wb++, q);
+      std::stable_sort(ws.begin(), ws.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) {
+        return x.first > y.first || (x.first == y.first && x.second < y.second);
+      });
+      for (int j = 0; j < o.wcap; ++j) {
+        const bool in = size_t(j) < ws.size();
+        if (o.schmidt) o.schmidt[at * o.wcap + j] = in ? ws[j].first : 0.0;
+        if (o.sector) o.sector[at * o.wcap + j] = in ? ws[j].second : -1;
+      }
+    }
 }
 
 }  // namespace obs

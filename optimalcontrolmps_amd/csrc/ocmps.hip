@@ -1804,8 +1804,11 @@ int ocg_get_state(ocg_ctx* c, int which, int t, int* dims, double* data, size_t 
 // driver on a workspace sized by its dry run, in chunks of at most half the
 // free device memory.  Reads the slots only.
 static constexpr size_t kObsKeepBytes = size_t(256) << 20;
+static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
+                         double* occ_buf, const obs::SpecOutputs* so);
+// With so the spectrum stages run too and their results go to *so.
 static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                         double* occ_buf) {
+                         double* occ_buf, const obs::SpecOutputs* so = nullptr) {
   const OcgParams& P = c->P;
   const int nst = int(slots.size());
   std::vector<obs::StateDesc> desc(nst);
@@ -1839,8 +1842,25 @@ static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0,
         bond[(out0 + i) * (P.L + 1) + b] = sum;
       }
   }
-  const obs::Want want = obs::want_of(o);
-  if (!want.norm && !want.env()) return 0;
+  return observe_descs(c, desc, out0, o, occ_buf, so);
+}
+
+// the chunks of observe.hpp's driver over states described on the device
+static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
+                         double* occ_buf, const obs::SpecOutputs* so) {
+  const OcgParams& P = c->P;
+  const int nst = int(desc.size());
+  obs::Want want = obs::want_of(o);
+  want.spec = so != nullptr;
+  if (!want.norm && !want.env() && !want.spec) return 0;
+  if (so) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
+    if (so->weights() && so->wcap < wb)
+      return fail(c, OCG_ECAP, "wcap " + std::to_string(so->wcap) + " below the largest bond dimension " +
+                                   std::to_string(wb));
+    if (wo > obs::kEigMaxOrder) return fail(c, OCG_ECAP, "spectrum: a bond sector above order 512");
+  }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
   const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want);
   const size_t budget = obs::chunk_budget();
@@ -1880,13 +1900,28 @@ static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0,
     std::vector<obs::Dest> dests;
     obs::Traffic tr;
     int rc = begin_kernel(c);
-    std::vector<double> res;
+    std::vector<double> res, ent, wts;
+    std::vector<int> status;
+    obs::Spec sp;
     if (!rc) {
-      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr);
+      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr);
       res.resize(2 * std::max<size_t>(dests.size(), 1));
       if (be.ok() && !dests.empty())
         be.note(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost,
                                c->stream));
+      if (so && be.ok()) {  // only results leave the device: the weights when they are asked for
+        ent.resize(std::max<size_t>(S.size() * (P.L - 1), 1));
+        status.resize(std::max<size_t>(sp.nstatus, 1));
+        wts.resize(so->weights() ? std::max<size_t>(sp.nw, 1) : 0);
+        if (P.L > 1)
+          be.note(hipMemcpyAsync(ent.data(), sp.d_ent, sizeof(double) * S.size() * (P.L - 1),
+                                 hipMemcpyDeviceToHost, c->stream));
+        if (sp.nstatus)
+          be.note(hipMemcpyAsync(status.data(), sp.d_status, sizeof(int) * sp.nstatus, hipMemcpyDeviceToHost,
+                                 c->stream));
+        if (so->weights() && sp.nw)
+          be.note(hipMemcpyAsync(wts.data(), sp.d_w, sizeof(double) * sp.nw, hipMemcpyDeviceToHost, c->stream));
+      }
       rc = end_kernel(c, 9);  // synchronises the stream
       if (!rc && !be.ok())
         rc = fail(c, be.overflow ? OCG_ENOMEM : OCG_EHIP,
@@ -1899,6 +1934,11 @@ static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0,
     c->obs_tr.bytes += tr.bytes;
     c->obs_tr.flops += tr.flops;
     c->obs_tr.launches += tr.launches;
+    if (so) {
+      for (size_t j = 0; j < sp.nstatus; ++j)
+        if (status[j]) return fail(c, OCG_ENUM, "spectrum: a Jacobi eigen block did not converge");
+      obs::scatter_spectrum(sp, S, os, P.L, P.Q1, ent.data(), wts.data(), *so);
+    }
     obs::scatter(dests, res.data(), o, occ_buf);
     if (o.nrows > 0 && (o.ada || o.nn))
       for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
@@ -1973,6 +2013,80 @@ int ocg_observe_states(ocg_ctx* c, int n, const int* dims, const double* const* 
       if (int rc = upload_mps(c, slots[i], dims + size_t(i0 + i) * P.nsq, data[i0 + i])) return rc;
     }
     if (int rc = observe_slots(c, slots, size_t(i0), o, bond, occ_buf)) return rc;
+  }
+  return 0;
+}
+
+int ocg_observe_spectrum(ocg_ctx* c, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
+                         int* sector) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_spectrum(c->hbm, which, ts, nt, wcap, entropy, schmidt, sector));
+  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
+  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
+  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
+  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
+  std::vector<int> slots(nt);
+  for (int i = 0; i < nt; ++i) {
+    const int t = ts ? ts[i] : i;
+    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
+    slots[i] = base + t;
+  }
+  if (nt == 0 || (!entropy && !schmidt && !sector)) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
+  return observe_slots(c, slots, 0, o, nullptr, nullptr, &so);
+}
+
+int ocg_observe_spectrum_states(ocg_ctx* c, int n, const int* dims, const double* const* data, int wcap,
+                                double* entropy, double* schmidt, int* sector) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_spectrum_states(c->hbm, n, dims, data, wcap, entropy, schmidt, sector));
+  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
+  if (n == 0 || (!entropy && !schmidt && !sector)) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const OcgParams& P = c->P;
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, P.L, P.p, 0, nullptr};
+  const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
+  for (int i = 0; i < n; ++i) {  // before anything is written
+    const int* d = dims + size_t(i) * P.nsq;
+    for (int j = 0; j < P.nsq; ++j)
+      if (d[j] < 0) return fail(c, OCG_EINVAL, "negative bond dimension");
+    for (int q = 0; q < P.Q1; ++q)
+      if (d[q] != (q == 0 ? 1 : 0) || d[P.L * P.Q1 + q] != (q == P.Q ? 1 : 0))
+        return fail(c, OCG_EINVAL, "bond 0 / bond L must be one state with q = 0 / q = Q");
+    for (int b = 1; b < P.L && so.weights(); ++b) {
+      long sum = 0;
+      for (int q = 0; q < P.Q1; ++q) sum += d[size_t(b) * P.Q1 + q];
+      if (sum > wcap) return fail(c, OCG_ECAP, "wcap below the largest bond dimension of the states");
+    }
+  }
+  // Staged a batch at a time in the compact interchange format itself: its blocks are
+  // the contiguous row-major matrices the descriptors want, and a sector may be larger
+  // than the Schmidt-rank bound of the pool slots (a padded or over-parametrised state).
+  const int B = std::min(n, 64);
+  for (int i0 = 0; i0 < n; i0 += B) {
+    const int nb = std::min(B, n - i0);
+    std::vector<obs::StateDesc> desc(nb);
+    std::vector<size_t> at(nb + 1, 0);
+    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims + size_t(i0 + i) * P.nsq);
+    double* d_st = nullptr;
+    if (hipMalloc((void**)&d_st, 16 * std::max<size_t>(at[nb], 1)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, OCG_ENOMEM, "spectrum: the staged states do not fit");
+    }
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < nb && e == hipSuccess; ++i) {
+      const int* d = dims + size_t(i0 + i) * P.nsq;
+      if (at[i + 1] > at[i])
+        e = hipMemcpyAsync(d_st + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
+      obs::compact_desc(P.L, P.p, P.Q, d, d_st + 2 * at[i], desc[i]);
+    }
+    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, &so)
+                             : fail(c, OCG_EHIP, std::string("spectrum: ") + hipGetErrorString(e));
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d_st);
+    if (rc) return rc;
   }
   return 0;
 }

@@ -294,6 +294,35 @@ class GpuTDMRG::Engine {
                   c, "ocg_observe");
     return o;
   }
+  // Entanglement spectra of the device-resident trajectory (ocg_observe_spectrum):
+  // the entropy of every bond b = 1..L-1 of the states ts (empty: all N) and,
+  // with weights, the Schmidt weights and their sectors (wcap = the largest
+  // bond dimension of the request).  The result carries ts, the bond dimensions
+  // and the spectrum fields; the other observables are those of observe().
+  TrajectoryObservables observeSpectrum(int which = 0, const std::vector<int>& ts = {}, bool weights = false) {
+    TrajectoryObservables o;
+    o.L = stepper.L;
+    o.p = stepper.p;
+    o.ts = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) o.ts.push_back(int(t));
+    const size_t nt = o.ts.size(), L = size_t(o.L), nb = L - 1;
+    o.bond.assign(nt * (L + 1), 0);
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_observe(c, which, o.ts.data(), int(nt), nullptr, 0, nullptr, nullptr, o.bond.data(), nullptr,
+                              nullptr),
+                  c, "ocg_observe");
+    if (weights) {
+      for (int b : o.bond) o.wcap = std::max(o.wcap, b);
+      o.schmidt.assign(nt * nb * o.wcap, 0.0);
+      o.sector.assign(nt * nb * o.wcap, -1);
+    }
+    o.entropy.assign(nt * nb, 0.0);
+    detail::check(ocg_observe_spectrum(c, which, o.ts.data(), int(nt), o.wcap, o.entropy.data(),
+                                       weights ? o.schmidt.data() : nullptr, weights ? o.sector.data() : nullptr),
+                  c, "ocg_observe_spectrum");
+    return o;
+  }
   std::vector<MPS> psiTrajectory() {
     std::vector<MPS> out;
     for (size_t t = 0; t < N; ++t)

@@ -73,7 +73,7 @@ struct MPS {
 };
 
 // Observables of nt trajectory states evaluated on the device (ocg_observe,
-// include/ocmps.h): what GpuTDMRG::Engine::observe and
+// ocg_observe_spectrum, include/ocmps.h): what GpuTDMRG::Engine::observe and
 // OptimalControl::getPsitObservables return and the overloads of
 // correlations.hpp read.  Entry e belongs to trajectory state ts[e].
 struct TrajectoryObservables {
@@ -85,7 +85,16 @@ struct TrajectoryObservables {
   std::vector<int> bond;      // [e][L+1] bond dimensions
   std::vector<Cplx> ada;      // [e][row][L] <a+_i a_j>, j >= i (0 for j < i)
   std::vector<double> nn;     // [e][row][L] <n_i n_j>, j >= i
+  // entanglement spectra (ocg_observe_spectrum); empty unless asked for
+  std::vector<double> entropy;  // [e][L-1] von Neumann entropy of the bonds b = 1..L-1
+  std::vector<double> schmidt;  // [e][L-1][wcap] raw Schmidt weights, descending, 0 past the bond dimension
+  std::vector<int> sector;      // [e][L-1][wcap] left particle count of each weight, -1 past the bond dimension
+  int wcap = 0;
   size_t size() const { return ts.size(); }
+  bool hasEntropy() const { return L > 1 && entropy.size() == ts.size() * size_t(L - 1) && !ts.empty(); }
+  double entropyAt(size_t e, int b) const { return entropy[e * (L - 1) + (b - 1)]; }
+  double schmidtAt(size_t e, int b, int j) const { return schmidt[(e * (L - 1) + (b - 1)) * wcap + j]; }
+  int sectorAt(size_t e, int b, int j) const { return sector[(e * (L - 1) + (b - 1)) * wcap + j]; }
   double occAt(size_t e, int site, int n) const { return occ[(e * L + (site - 1)) * p + n]; }
   int bondDim(size_t e, int b) const { return bond[e * (L + 1) + b]; }
   int maxBondDim(size_t e) const {

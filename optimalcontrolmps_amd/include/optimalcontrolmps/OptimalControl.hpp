@@ -12,7 +12,8 @@
 //   Engine: setShards(n), propagate(u, which), divT(), overlapFactor(),
 //           fidelities(), precomputeXiH(), hessianRows(u, F, divT, H),
 //           hessianFresh(u, F&, divT&, H) (all of the above for a new control), psiTrajectory(),
-//           observe(which, ts, rows) (optional: getPsitObservables needs it),
+//           observe(which, ts, rows), observeSpectrum(which, ts, weights) (optional: getPsitObservables
+//           needs the first, and the second when entropies are asked for),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -60,10 +61,14 @@ class OptimalControl {
   // occupation distributions, bond dimensions and a+a / nn correlation rows of
   // psi_t for t in ts (empty: all), rows = start sites 1..L (correlations.hpp
   // has the reference-named overloads that read the result).  Only for
-  // steppers whose Engine has observe() (GpuTDMRG).
+  // steppers whose Engine has observe() (GpuTDMRG).  entropy: also the
+  // entanglement entropy of every bond (AnalyzeQuench's entanglementEntropy
+  // loop; Engine::observeSpectrum), read by entanglementEntropy(obs, e).
   ocmps::TrajectoryObservables getPsitObservables(const std::vector<int>& ts = {},
-                                                  const std::vector<int>& rows = {}) const {
-    return engine->observe(0, ts, rows);
+                                                  const std::vector<int>& rows = {}, bool entropy = false) const {
+    ocmps::TrajectoryObservables o = engine->observe(0, ts, rows);
+    if (entropy) o.entropy = engine->observeSpectrum(0, ts, false).entropy;
+    return o;
   }
   size_t getM() const { return M; }
   size_t getN() const { return N; }

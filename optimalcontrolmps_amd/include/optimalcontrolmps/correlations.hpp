@@ -16,7 +16,10 @@
 //
 // The overloads taking a TrajectoryObservables read what the device computed
 // for the stored trajectory (OptimalControl::getPsitObservables): the loops
-// over getPsit() of the drivers without copying a state to the host.
+// over getPsit() of the drivers without copying a state to the host,
+// entanglementEntropy(obs, e) included when the entropies were asked for
+// (getPsitObservables(ts, rows, true): ocg_observe_spectrum, weights
+// eig(S^H R S) with the device's environments, which carry no conjugate).
 //
 // The MPS functions are host code (analysis of single states).  The
 // contractions are exact and gauge-free: left and right environments are
@@ -373,6 +376,14 @@ inline double correlationTerm(const BoseHubbard& sites, const MPS& psi, const st
     for (int j = 0; j < N; ++j) A[size_t(i) * N + j] = rho[i][j];
   const std::vector<double> w = obs::heev(A, N);
   return *std::max_element(w.begin(), w.end());
+}
+
+// the entropies the device computed for entry e (bonds b = 1..N-1); throws
+// std::invalid_argument when they were not requested
+inline std::vector<double> entanglementEntropy(const TrajectoryObservables& o, size_t e) {
+  if (!o.hasEntropy() || e >= o.size())
+    throw std::invalid_argument("entanglementEntropy(TrajectoryObservables): entropies were not requested");
+  return std::vector<double>(o.entropy.begin() + e * (o.L - 1), o.entropy.begin() + (e + 1) * (o.L - 1));
 }
 
 // S_b = -sum p ln p over the Schmidt weights of bond b = 1..N-1 (weights

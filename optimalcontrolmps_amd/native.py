@@ -44,8 +44,10 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
         flags.append(f"-DOCG_NT={int(nt)}")
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
-                  "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp"],
-        "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp"],
+                  "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
+                  "observe_eig.hpp"],
+        "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
+                "observe_eig.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -127,6 +129,8 @@ SIGNATURES = [
     ("ocg_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_size_t, szp]),
     ("ocg_observe", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, ip, C.c_int, dp, dp, ip, dp, dp]),
     ("ocg_observe_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), ip, C.c_int, dp, dp, ip, dp, dp]),
+    ("ocg_observe_spectrum", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.c_int, dp, dp, ip]),
+    ("ocg_observe_spectrum_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), C.c_int, dp, dp, ip]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -493,6 +497,49 @@ class Engine:
         data = (dp * n)(*[r.ctypes.data_as(dp) for r in raws])
         self._chk(lib().ocg_observe_states(self.h, n, dims.ctypes.data_as(ip), data, pr, len(rr),
                                            *self._observe_ptrs(out, len(rr))), "ocg_observe_states")
+        return out
+
+    SPECTRUM_OUTPUTS = ("entropy", "schmidt", "sector")
+
+    def _spectrum_out(self, n, wcap, outputs):
+        bad = set(outputs) - set(self.SPECTRUM_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown spectrum outputs {sorted(bad)}")
+        nb = self.L - 1
+        full = {"entropy": lambda: np.zeros((n, nb)), "schmidt": lambda: np.zeros((n, nb, wcap)),
+                "sector": lambda: np.full((n, nb, wcap), -1, np.int32)}
+        out = {k: full[k]() for k in self.SPECTRUM_OUTPUTS if k in outputs}
+        ptr = lambda k, t: out[k].ctypes.data_as(t) if k in out else None
+        return out, (ptr("entropy", dp), ptr("schmidt", dp), ptr("sector", ip))
+
+    def spectrum(self, which=0, ts=None, outputs=SPECTRUM_OUTPUTS):
+        """Entanglement spectra of the device trajectory states (ocg_observe_spectrum):
+        which / ts as observe().  Returns a dict of numpy arrays: entropy (nt, L-1) at
+        the bonds b = 1..L-1, schmidt (nt, L-1, wcap) the raw Schmidt weights of each
+        bond (their sum is norm2), descending and padded with 0, and sector
+        (nt, L-1, wcap) the left particle count of each weight, padded with -1; wcap is
+        the largest bond dimension of the request.  `outputs` selects a subset."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        wcap = 0
+        if len(tt) and ("schmidt" in outputs or "sector" in outputs):
+            wcap = int(self.observe(which, tt, outputs=("bond",))["bond"].max())
+        out, ptrs = self._spectrum_out(len(tt), wcap, outputs)
+        self._chk(lib().ocg_observe_spectrum(self.h, int(which), pt, len(tt), wcap, *ptrs), "ocg_observe_spectrum")
+        return out
+
+    def spectrum_states(self, states, outputs=SPECTRUM_OUTPUTS):
+        """spectrum() for caller-supplied host states of any gauge or norm
+        (ocg_observe_spectrum_states)."""
+        n = len(states)
+        wcap = max([int(m.bond_dims().max()) for m in states], default=0)
+        out, ptrs = self._spectrum_out(n, wcap, outputs)
+        if n == 0:
+            return out
+        dims = np.ascontiguousarray(np.concatenate([m.dims for m in states]).astype(np.int32))
+        raws = [np.ascontiguousarray(m.raw()) for m in states]
+        data = (dp * n)(*[r.ctypes.data_as(dp) for r in raws])
+        self._chk(lib().ocg_observe_spectrum_states(self.h, n, dims.ctypes.data_as(ip), data, wcap, *ptrs),
+                  "ocg_observe_spectrum_states")
         return out
 
     def stats(self, kind):

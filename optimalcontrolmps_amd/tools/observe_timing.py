@@ -2,7 +2,7 @@
 was before: one ocg_get_state copy per state (a lower bound of that path, which
 adds the host contraction of correlations.hpp on top).
 
-    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|all] [--reps R] [--out DIR]
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|all] [--reps R] [--out DIR]
 
 One process; every shape is warmed up; each timed call ends in a device
 synchronise (both entry points return only after their results are on the
@@ -11,6 +11,13 @@ reported.  Config 1: L=5, p=5, chi<=80, N_t=201, the LDS engine.  Config 4
 slice: L=20, p=7, chi=256 from the warm state, N_t=33, the HBM engine; also the
 old path's cost for one state (copy + host expectationValues).  Writes
 observe_config1.json / observe_config4.json into --out (default profiles/).
+
+s1 / s4: the entanglement spectra (ocg_observe_spectrum) at the same two
+shapes, entropies only and with the weights, alternating with the copy loop;
+the path they replace is that loop plus N_t times the host
+entanglementEntropy(sites, psi) of one mid-trajectory state, timed by a small
+stand-alone program.  Writes observe_spectrum_config1.json /
+observe_spectrum_config4.json.
 """
 from __future__ import annotations
 
@@ -81,11 +88,12 @@ def config1(reps):
     return res
 
 
-def host_expectation_seconds(state):
-    """copy-free part of the old path for one state: expectationValues(sites, psi, "N") on the host"""
-    src = os.path.join(native.PKG_DIR, "tools", "host_expectation_timing.cpp")
+def host_expectation_seconds(state, tool="host_expectation_timing"):
+    """copy-free part of the old path for one state: expectationValues(sites, psi, "N") (or, with
+    tool="host_entropy_timing", entanglementEntropy(sites, psi)) on the host"""
+    src = os.path.join(native.PKG_DIR, "tools", tool + ".cpp")
     with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "host_expectation_timing")
+        exe = os.path.join(d, tool)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, src])
         path = os.path.join(d, "state.bin")
         with open(path, "wb") as f:
@@ -125,18 +133,89 @@ def config4(reps):
     return res
 
 
+def spectrum_cases(eng, Nt, reps, warm):
+    """spectrum (entropies only / with the weights), the environments alone (observe occ) and the copy loop,
+    alternating; kind 9 (and kind 7) per case from a pass of its own"""
+    dims = np.zeros((eng.L + 1) * (eng.Q + 1), np.int32)
+    data = np.zeros(2 * eng.cap)
+    cases = {"spectrum_entropy": lambda: eng.spectrum(0, None, outputs=("entropy",)),
+             "spectrum_weights": lambda: eng.spectrum(0, None),
+             "observe_occ": lambda: eng.observe(0, None, (), outputs=("occ",)),
+             "get_state_copies": lambda: copy_all(eng, 0, Nt, dims, data)}
+    for f in cases.values():
+        for _ in range(warm):
+            f()
+    t = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    res = {k: spread(v) for k, v in t.items()}
+    for k in ("spectrum_entropy", "observe_occ"):
+        eng.reset_stats()
+        cases[k]()
+        res[k + "_kind9"] = eng.stats(9)
+        res[k + "_kind7_ms"] = eng.stats(7)["ms"]
+    host = host_expectation_seconds(eng.state(0, Nt // 2), "host_entropy_timing")
+    res["host_entanglementEntropy_one_state"] = host
+    old = res["get_state_copies"]["median_ms"] + Nt * 1e3 * host["seconds"]
+    res["old_path_ms"] = old
+    for k in ("spectrum_entropy", "spectrum_weights"):
+        res[k + "_vs_old_path"] = old / res[k]["median_ms"]
+        res[k + "_vs_copies"] = res["get_state_copies"]["median_ms"] / res[k]["median_ms"]
+    # kind 9 of the entropies-only call: its stream time, the k_gemm time inside (kind 7; HBM engine only) and
+    # the rest (eigen stages, entropy reduction, the gaps in which the host builds the next task lists).  The
+    # occupations call forms the same environments (plus the X products and a close launch per site instead of
+    # the spectrum stages), so the difference of the two rests estimates the eigen stages; it is no clean split.
+    a, b = res["spectrum_entropy_kind9"], res["observe_occ_kind9"]
+    ga, gb = res["spectrum_entropy_kind7_ms"], res["observe_occ_kind7_ms"]
+    res["kind9_split_ms"] = {"total": a["ms"], "k_gemm": ga, "rest": a["ms"] - ga,
+                             "occupations_call_total": b["ms"], "occupations_call_k_gemm": gb,
+                             "eigen_and_entropy_estimate": (a["ms"] - ga) - (b["ms"] - gb)}
+    return res
+
+
+def spectrum1(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    eng.propagate(np.linspace(2.5, 50.0, Nt), 1)
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine (no k_gemm: kind 7 is 0)",
+           "bond_max": int(eng.observe(0, None, (), outputs=("bond",))["bond"].max())}
+    res.update(spectrum_cases(eng, Nt, reps, 2))
+    return res
+
+
+def spectrum4(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 20, 7, 20, 1.0, 0.005, 1e-8, 256, 33
+    z = np.load(os.path.join(GOLDEN, "c4_warm256.npz"), allow_pickle=False)
+    c4 = np.load(os.path.join(GOLDEN, "c4.npz"), allow_pickle=False)
+    u = np.load(os.path.join(GOLDEN, "c4_w256h33.npz"), allow_pickle=False)["u"]
+    eng = Engine(L, p, Q, J, dt, cut, maxm, engine="hbm")
+    eng.set_states(MPS(L, p, Q, c4["w256h/tgt_dims"], c4["w256h/tgt_data"]), MPS(L, p, Q, z["dims"], z["data"]))
+    eng.propagate(u, 1)
+    res = {"config": "4 slice: L=20 p=7 Q=20 chi=256 (warm state) N_t=33, HBM engine",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1)))}
+    res.update(spectrum_cases(eng, Nt, reps, 1))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", default="all", choices=["1", "4", "all"])
+    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
-    for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4))):
+    for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4)),
+                           ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4))):
         if a.config in (name, "all"):
             res = fn(reps)
             res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
-            with open(os.path.join(a.out, f"observe_config{name}.json"), "w") as f:
+            out = f"observe_spectrum_config{name[1:]}.json" if name.startswith("s") else f"observe_config{name}.json"
+            with open(os.path.join(a.out, out), "w") as f:
                 json.dump(res, f, indent=1)
             print(json.dumps(res))
 
