@@ -82,8 +82,9 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * ocg_hessian when OCG_HBM_PIPE=1 forces a pipeline that cannot allocate;
  * 3 ocg_get_info_sz, ocg_get_path_stats, ocg_abi_version (round 6);
  * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9;
- * 5 ocg_observe_spectrum, ocg_observe_spectrum_states. */
-#define OCG_ABI_VERSION 5
+ * 5 ocg_observe_spectrum, ocg_observe_spectrum_states;
+ * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states. */
+#define OCG_ABI_VERSION 6
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
 int ocg_set_tstep(ocg_ctx* ctx, double tstep);
@@ -271,6 +272,52 @@ int ocg_observe_spectrum(ocg_ctx* ctx, int which, const int* ts, int nt, int wca
 int ocg_observe_spectrum_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, int wcap,
                                 double* entropy, double* schmidt, int* sector);
 
+/* Projective occupation snapshots of the device-resident trajectory states: nshots
+ * samples n = (n_1 .. n_L) per state drawn from |<n|s>|^2 / <s|s> (what a
+ * quantum-gas microscope records), drawn where the states are.  which, ts and the
+ * existence rules are those of ocg_observe; any gauge and any norm.  With A_k(q, n)
+ * the blocks and Renv the right environments of ocg_observe (Renv_L[Q] = 1) a shot
+ * runs left to right from v = [1], q = 0; at site k = 1..L
+ *   w_n  = v A_k(q, n)                                  (a row vector)
+ *   pr_n = max(Re(w_n Renv_k[q+n] w_n^H), 0)            (0 without a block or Renv)
+ *   c_n  = pr_0 + .. + pr_n (added in that order), S = c_{p-1}
+ * and the draw is the smallest n with u S < c_n (if rounding leaves none, the
+ * largest n with pr_n > 0); then v = w_n, q += n.  Nothing is renormalised on the
+ * way.  logp = ln |v|^2 - ln norm2 with the final 1 x 1 v and norm2 = the S of
+ * site 1 (= Renv_0[0] = <s|s>).  A shot that meets S == 0 (a zero state) has -1 at
+ * every site and logp = -inf; that is no error.
+ * Random numbers are counter-based: with mix the splitmix64 step
+ *   x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *   x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^= x >> 31
+ * h = mix(mix(mix(mix(seed) ^ id) ^ shot) ^ k), u = (h >> 11) * 2^-53, id = ts[e]
+ * (the state index; the position i for ocg_sample_states), shot = 0..nshots-1,
+ * k = 1..L.  So the same t requested twice gives the same shots, the first m
+ * shots of a larger request are those of a request of m, and which is not mixed
+ * in (vary the seed).  A shot is bit-identical whatever else is requested with it
+ * and however the request is chunked.
+ * Outputs: config[nt][nshots][L] occupations; logp[nt][nshots] (NULL: skipped).
+ * nshots < 0: OCG_EINVAL; nshots == 0 writes nothing.  Bond sectors of order up
+ * to 512 (OCG_ECAP above).  Chunked as ocg_observe (OCG_ENOMEM if one state's
+ * workspace does not fit); only the results leave the device.  Reads the
+ * trajectories only. */
+int ocg_sample(ocg_ctx* ctx, int which, const int* ts, int nt, int nshots, unsigned long long seed,
+               signed char* config, double* logp);
+/* The same for n caller-supplied host states (as ocg_observe_spectrum_states: any
+ * gauge or norm; a sector may be larger than its Schmidt-rank bound), staged on the
+ * device in batches; id = the position of the state in the call. */
+int ocg_sample_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, int nshots,
+                      unsigned long long seed, signed char* config, double* logp);
+/* Amplitudes <n|s> of given configurations: the chain v -> v A_k(q, n_k) of
+ * ocg_sample with the n given and no Renv (no right sweep), amp = the final 1 x 1
+ * v; 0 when the path meets a missing block.  Raw: the sum of |amp|^2 over all
+ * configurations is norm2.  configs[nconf][L]; an entry outside 0..p-1 or a
+ * configuration that does not hold Q particles: OCG_EINVAL.
+ * amp[nt][nconf][2], interleaved (re, im).  nconf == 0 writes nothing. */
+int ocg_fock_amplitudes(ocg_ctx* ctx, int which, const int* ts, int nt, const signed char* configs, int nconf,
+                        double* amp);
+int ocg_fock_amplitudes_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data,
+                               const signed char* configs, int nconf, double* amp);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -305,7 +352,8 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * OCG_HBM_PIPE=1, which makes any pipeline failure the call's status),
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
  * segment length of the last one), 9 the observable kernels of ocg_observe /
- * ocg_observe_states / ocg_observe_spectrum[_states] (HIP-event time of their chunks, kernel launches, and the
+ * ocg_observe_states / ocg_observe_spectrum[_states] / ocg_sample[_states] /
+ * ocg_fock_amplitudes[_states] (HIP-event time of their chunks, kernel launches, and the
  * algorithmic bytes and flops of the host-built task lists).  Sums since the
  * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,

@@ -3197,6 +3197,9 @@ struct ObsBackend {
     }
     t.clear();
   }
+  void sample(obs::SampleTable& tb, const obs::SArgs& a) {
+    HCK(obs::sample_launch(tb, a, E.st, [&](auto& v) { return E.upload(v); }));
+  }
 };
 
 obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
@@ -3220,10 +3223,11 @@ obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
 // the observables of state slots[i] into entry out0 + i of the outputs, in
 // chunks whose workspace fits half the free HBM
 void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so);
-// with so the spectrum stages run too and their results go to *so
+                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr);
+// with so the spectrum stages run too and their results go to *so; with sn the snapshot
+// launch follows the right sweep instead and its results go to sn's outputs
 void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                   double* occ_buf, const obs::SpecOutputs* so = nullptr) {
+                   double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
   hbm::Engine& E = *h->E;
   const int L = E.L, nst = int(slots.size());
   std::vector<obs::StateDesc> desc(nst);
@@ -3232,17 +3236,22 @@ void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, co
     if (bond)
       for (int b = 0; b <= L; ++b) bond[(out0 + i) * (L + 1) + b] = E.states[slots[i]].dims.bond(b);
   }
-  observe_descs(h, desc, out0, o, occ_buf, so);
+  observe_descs(h, desc, out0, o, occ_buf, so, sn);
 }
 
 // the chunks of observe.hpp's driver over states described on the device
 void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so) {
+                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn) {
   hbm::Engine& E = *h->E;
   const int L = E.L, nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec) return;
+  if (!want.norm && !want.env() && !want.spec && !sn) return;
+  if (sn) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
+    if (wo > obs::kSampleMaxOrder) throw hbm::Error(2, "snapshots: a bond sector above order 512");
+  }
   if (so) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
@@ -3252,12 +3261,15 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     if (wo > obs::kEigMaxOrder) throw hbm::Error(2, "spectrum: a bond sector above order 512");
   }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want);
+  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want, sn);
   const size_t budget = obs::chunk_budget();
   for (int i0 = 0; i0 < nst;) {
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
+    if (sn && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      throw hbm::Error(6, "snapshots: the workspace of one state (" + std::to_string(sum) +
+                              " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
@@ -3268,7 +3280,9 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     std::vector<obs::Dest> dests;
     Timer t(h, 9);
     obs::Spec sp;
-    const double* d_out = obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr);
+    const double* d_out =
+        obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr, sn);
+    if (sn) HCK(sn->fetch(out0 + i0, S.size(), L, E.st));
     std::vector<double> res(2 * std::max<size_t>(dests.size(), 1));
     if (!dests.empty())
       HCK(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost, E.st));
@@ -3311,6 +3325,55 @@ void observe_check_rows(const hbm::Engine& E, const int* rows, int nrows) {
   if (nrows < 0 || (nrows > 0 && !rows)) throw hbm::Error(1, "bad rows");
   for (int i = 0; i < nrows; ++i)
     if (rows[i] < 1 || rows[i] > E.L) throw hbm::Error(1, "row (start site) out of 1..L");
+}
+
+// the dims of caller-supplied states, before anything is written (wcap >= 0: the
+// bond dimensions must fit it)
+void staged_check(const hbm::Engine& E, int n, const int* dims, int wcap) {
+  const int nsq = (E.L + 1) * E.Q1;
+  for (int i = 0; i < n; ++i) {
+    const int* d = dims + size_t(i) * nsq;
+    for (int j = 0; j < nsq; ++j)
+      if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
+    for (int q = 0; q < E.Q1; ++q)
+      if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
+        throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
+    for (int b = 1; b < E.L && wcap >= 0; ++b) {
+      long sum = 0;
+      for (int q = 0; q < E.Q1; ++q) sum += d[size_t(b) * E.Q1 + q];
+      if (sum > wcap) throw hbm::Error(2, "wcap below the largest bond dimension of the states");
+    }
+  }
+}
+
+// Caller-supplied states staged a batch at a time in the compact interchange format
+// itself: its blocks are the contiguous row-major matrices the descriptors want, and a
+// sector may be larger than the Hilbert-space bound of the state slots (a padded or
+// over-parametrised state).
+void observe_staged(hbm_engine* h, int n, const int* dims, const double* const* data, const obs::Outputs& o,
+                    const obs::SpecOutputs* so, obs::Snap* sn) {
+  hbm::Engine& E = *h->E;
+  const int nsq = (E.L + 1) * E.Q1;
+  const int B = std::min(n, 64);
+  for (int i0 = 0; i0 < n; i0 += B) {
+    const int nb = std::min(B, n - i0);
+    std::vector<size_t> at(nb + 1, 0);
+    for (int i = 0; i < nb; ++i) {
+      obs::StateDesc tmp;
+      at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, nullptr, tmp);
+    }
+    hbm::DBuf<double> stage;
+    stage.reserve(2 * std::max<size_t>(at[nb], 1));
+    std::vector<obs::StateDesc> desc(nb);
+    for (int i = 0; i < nb; ++i) {
+      if (at[i + 1] > at[i])
+        HCK(hipMemcpyAsync(stage.p + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
+                           E.st));
+      obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, stage.p + 2 * at[i], desc[i]);
+    }
+    observe_descs(h, desc, size_t(i0), o, nullptr, so, sn);
+    E.sync();
+  }
 }
 }  // namespace
 
@@ -3412,45 +3475,117 @@ int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const dou
     hbm::Engine& E = *h->E;
     if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
     if (n == 0 || (!entropy && !schmidt && !sector)) return;
-    const int nsq = (E.L + 1) * E.Q1;
     const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
     const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-    for (int i = 0; i < n; ++i) {  // before anything is written
-      const int* d = dims + size_t(i) * nsq;
-      for (int j = 0; j < nsq; ++j)
-        if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
-      for (int q = 0; q < E.Q1; ++q)
-        if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
-          throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
-      for (int b = 1; b < E.L && so.weights(); ++b) {
-        long sum = 0;
-        for (int q = 0; q < E.Q1; ++q) sum += d[size_t(b) * E.Q1 + q];
-        if (sum > wcap) throw hbm::Error(2, "wcap below the largest bond dimension of the states");
-      }
+    staged_check(E, n, dims, so.weights() ? std::max(wcap, 0) : -1);
+    observe_staged(h, n, dims, data, o, &so, nullptr);
+  });
+}
+
+namespace {
+// the trajectory slots of a request (which / ts as hbm_observe)
+std::vector<int> trajectory_slots(hbm_engine* h, int which, const int* ts, int nt,
+                                  std::vector<unsigned long long>* ids) {
+  if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
+  const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
+  if (!ok) throw hbm::Error(4, "requested trajectory not available");
+  const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
+  std::vector<int> slots(nt);
+  if (ids) ids->resize(nt);
+  for (int i = 0; i < nt; ++i) {
+    const int t = ts ? ts[i] : i;
+    if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
+    slots[i] = base + t;
+    if (ids) (*ids)[i] = (unsigned long long)t;
+  }
+  return slots;
+}
+
+// every configuration has entries in 0..p-1 that add up to Q
+void check_configs(const hbm::Engine& E, const signed char* configs, int nconf, double* amp) {
+  if (nconf < 0 || (nconf > 0 && (!configs || !amp))) throw hbm::Error(1, "bad configurations / outputs");
+  for (int j = 0; j < nconf; ++j) {
+    int sum = 0;
+    for (int k = 0; k < E.L; ++k) {
+      const int v = configs[size_t(j) * E.L + k];
+      if (v < 0 || v >= E.p) throw hbm::Error(1, "a configuration entry outside 0..p-1");
+      sum += v;
     }
-    // Staged a batch at a time in the compact interchange format itself: its blocks are
-    // the contiguous row-major matrices the descriptors want, and a sector may be larger
-    // than the Hilbert-space bound of the state slots (a padded or over-parametrised state).
-    const int B = std::min(n, 64);
-    for (int i0 = 0; i0 < n; i0 += B) {
-      const int nb = std::min(B, n - i0);
-      std::vector<size_t> at(nb + 1, 0);
-      for (int i = 0; i < nb; ++i) {
-        obs::StateDesc tmp;
-        at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, nullptr, tmp);
-      }
-      hbm::DBuf<double> stage;
-      stage.reserve(2 * std::max<size_t>(at[nb], 1));
-      std::vector<obs::StateDesc> desc(nb);
-      for (int i = 0; i < nb; ++i) {
-        if (at[i + 1] > at[i])
-          HCK(hipMemcpyAsync(stage.p + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
-                             E.st));
-        obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, stage.p + 2 * at[i], desc[i]);
-      }
-      observe_descs(h, desc, size_t(i0), o, nullptr, &so);
-      E.sync();
-    }
+    if (sum != E.Q) throw hbm::Error(1, "a configuration that does not hold Q particles");
+  }
+}
+}  // namespace
+
+int hbm_sample(hbm_engine* h, int which, const int* ts, int nt, int nshots, unsigned long long seed,
+               signed char* config, double* logp) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (nshots < 0 || (nshots > 0 && nt > 0 && !config)) throw hbm::Error(1, "bad shots / outputs");
+    std::vector<unsigned long long> ids;
+    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, &ids);
+    if (nt == 0 || nshots == 0) return;
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    obs::Snap sn;
+    sn.nper = nshots;
+    sn.seed = seed;
+    sn.ids = ids.data();
+    sn.config = config;
+    sn.val = logp;
+    observe_slots(h, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+  });
+}
+
+int hbm_sample_states(hbm_engine* h, int n, const int* dims, const double* const* data, int nshots,
+                      unsigned long long seed, signed char* config, double* logp) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
+    if (nshots < 0 || (nshots > 0 && n > 0 && !config)) throw hbm::Error(1, "bad shots / outputs");
+    if (n == 0 || nshots == 0) return;
+    staged_check(E, n, dims, -1);
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    std::vector<unsigned long long> ids(n);
+    for (int i = 0; i < n; ++i) ids[i] = (unsigned long long)i;
+    obs::Snap sn;
+    sn.nper = nshots;
+    sn.seed = seed;
+    sn.ids = ids.data();
+    sn.config = config;
+    sn.val = logp;
+    observe_staged(h, n, dims, data, o, nullptr, &sn);
+  });
+}
+
+int hbm_fock_amplitudes(hbm_engine* h, int which, const int* ts, int nt, const signed char* configs, int nconf,
+                        double* amp) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
+    check_configs(E, configs, nconf, amp);
+    if (nt == 0 || nconf == 0) return;
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    obs::Snap sn;
+    sn.nper = nconf;
+    sn.given = configs;
+    sn.val = amp;
+    observe_slots(h, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+  });
+}
+
+int hbm_fock_amplitudes_states(hbm_engine* h, int n, const int* dims, const double* const* data,
+                               const signed char* configs, int nconf, double* amp) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
+    check_configs(E, configs, nconf, amp);
+    if (n == 0 || nconf == 0) return;
+    staged_check(E, n, dims, -1);
+    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    obs::Snap sn;
+    sn.nper = nconf;
+    sn.given = configs;
+    sn.val = amp;
+    observe_staged(h, n, dims, data, o, nullptr, &sn);
   });
 }
 

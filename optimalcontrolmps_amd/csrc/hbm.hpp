@@ -67,6 +67,16 @@ int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* cons
 // ocg_observe_spectrum / ocg_observe_spectrum_states (observe.hpp's spectrum stages, observe_eig.hpp's kernels)
 int hbm_observe_spectrum(hbm_engine* h, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
                          int* sector);
+// ocg_sample / ocg_fock_amplitudes and their _states variants (observe_sample.hpp's kernel after
+// observe.hpp's right sweep)
+int hbm_sample(hbm_engine* h, int which, const int* ts, int nt, int nshots, unsigned long long seed,
+               signed char* config, double* logp);
+int hbm_sample_states(hbm_engine* h, int n, const int* dims, const double* const* data, int nshots,
+                      unsigned long long seed, signed char* config, double* logp);
+int hbm_fock_amplitudes(hbm_engine* h, int which, const int* ts, int nt, const signed char* configs, int nconf,
+                        double* amp);
+int hbm_fock_amplitudes_states(hbm_engine* h, int n, const int* dims, const double* const* data,
+                               const signed char* configs, int nconf, double* amp);
 int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const double* const* data, int wcap,
                                 double* entropy, double* schmidt, int* sector);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM

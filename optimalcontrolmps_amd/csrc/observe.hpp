@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "observe_eig.hpp"
+#include "observe_sample.hpp"
 
 namespace obs {
 
@@ -83,6 +84,30 @@ struct Spec {
   int* d_status = nullptr;   // one word per eigen block, nonzero: not converged
   size_t nw = 0, nstatus = 0;
   std::vector<size_t> woff;  // [state * (L-1) + b-1]: where bond b's weights start in d_w
+};
+// a snapshot request (ocg_sample: draw nper shots per state; ocg_fock_amplitudes: the
+// amplitudes of the nper given configurations) and the results of one chunk
+struct Snap {
+  int nper = 0;
+  bool amp() const { return given != nullptr; }
+  // queue the copies of a chunk's results (states out0..out0+nst of the request) to the host
+  hipError_t fetch(size_t out0, size_t nst, int L, hipStream_t st) const {
+    const size_t items = nst * nper, at = out0 * nper;
+    hipError_t e = hipSuccess;
+    if (!amp() && items)
+      e = hipMemcpyAsync(config + at * L, d_config, items * L, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && val && items)
+      e = hipMemcpyAsync(val + at * (amp() ? 2 : 1), d_val, sizeof(double) * items * (amp() ? 2 : 1),
+                         hipMemcpyDeviceToHost, st);
+    return e;
+  }
+  unsigned long long seed = 0;
+  const unsigned long long* ids = nullptr;  // [out slot]: the id mixed into a state's random numbers
+  const signed char* given = nullptr;       // host [nper][L]: amplitude mode (no right sweep)
+  signed char* config = nullptr;            // host outputs by out slot: [nper][L] each (draw mode),
+  double* val = nullptr;                    // logp [nper] (may be null) or amplitudes [nper][2] each
+  signed char* d_config = nullptr;          // device [state][nper][L] (draw mode)
+  double* d_val = nullptr;                  // device: logp [state][nper], or amplitudes [state][nper][2]
 };
 // where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn
 struct Dest {
@@ -199,6 +224,7 @@ __global__ __launch_bounds__(kCloseNT) void k_obs_close(const CTask* __restrict_
 //   void close(std::vector<CTask>&, std::vector<Pair>&, double* out)
 //   int eig(std::vector<ETask>&, int* status)     one eigen stage; returns its launches
 //   void entropy(std::vector<STask>&, double* out)
+//   void sample(SampleTable&, const SArgs&)          the snapshot launch of the chunk
 
 // dry run: the workspace a chunk would take (256-byte granules, as the arenas)
 struct CountBackend {
@@ -232,6 +258,10 @@ struct CountBackend {
   void entropy(std::vector<STask>& t, double*) {
     bytes += al(sizeof(STask) * t.size());
     t.clear();
+  }
+  void sample(SampleTable& tb, const SArgs&) {
+    bytes += al(sizeof(SBlk) * tb.blk.size()) + al(sizeof(double*) * tb.renv.size()) +
+             al(sizeof(SState) * tb.st.size()) + al(tb.given.size());
   }
 };
 
@@ -334,6 +364,9 @@ struct RawBackend {
     }
     t.clear();
   }
+  void sample(SampleTable& tb, const SArgs& a) {
+    if (ok()) note(sample_launch(tb, a, st, [&](auto& v) { return upload(v); }));
+  }
 };
 
 // ------------------------------------------------------------------ driver
@@ -354,10 +387,10 @@ inline size_t max_outputs(int L, int p, int nrows, Want w) {
 template <class BE>
 double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc*>& S,
                   const std::vector<size_t>& out_slot, const std::vector<int>& rows, Want want,
-                  std::vector<Dest>& dests, Traffic& tr, Spec* spec = nullptr) {
+                  std::vector<Dest>& dests, Traffic& tr, Spec* spec = nullptr, Snap* snap = nullptr) {
   const int Q1 = Q + 1, B = int(S.size()), R = int(rows.size());
   const bool ada = want.ada && R > 0, nn = want.nn && R > 0, env = want.occ || ada || nn;
-  const bool renv = env || spec != nullptr;
+  const bool renv = env || spec != nullptr || (snap && !snap->given);
   dests.clear();
   double* d_out = be.alloc(size_t(B) * max_outputs(L, p, R, want));
   const double* one = be.one();
@@ -428,6 +461,45 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
         }
       launch_gemm();
     }
+  }
+
+  // ---- snapshots: the table of every block and right environment, then one launch
+  if (snap) {
+    SampleTable tb;
+    const bool amp = snap->given != nullptr;
+    int vmax = 1;
+    double work = 0;  // complex multiply-adds of one shot along the widest sectors
+    for (int i = 0; i < B; ++i) {
+      tb.st.push_back(SState{snap->ids ? snap->ids[out_slot[i]] : 0ull, (long long)tb.blk.size(),
+                             (long long)tb.renv.size()});
+      for (int k = 1; k <= L; ++k) {
+        double site = 0;
+        for (int q = 0; q <= Q; ++q) {
+          double sec = 0;
+          for (int n = 0; n < p; ++n) {
+            const Blk a = A(i, k, q, n);
+            tb.blk.push_back(SBlk{a.p, a.r, a.c});
+            if (!a.p) continue;
+            vmax = std::max(vmax, std::max(a.r, a.c));
+            const double rc = double(a.r) * a.c, cc = double(a.c) * a.c;
+            sec = amp ? std::max(sec, rc) : sec + rc + cc + rc / p;
+          }
+          site = std::max(site, sec);
+        }
+        work += site;
+        for (int q = 0; q <= Q; ++q) tb.renv.push_back(amp ? nullptr : Renv[i][size_t(k) * Q1 + q]);
+      }
+    }
+    const size_t items = size_t(B) * snap->nper;
+    snap->d_config = amp ? nullptr : reinterpret_cast<signed char*>(be.alloc((items * L + 15) / 16));
+    snap->d_val = be.alloc(amp ? items : (items + 1) / 2);
+    if (amp) tb.given.assign(snap->given, snap->given + size_t(snap->nper) * L);
+    tr.flops += 8.0 * work / B * double(items);
+    tr.bytes += 16.0 * work / B * double(items) + (amp ? 16.0 : 8.0 + L) * double(items);
+    ++tr.launches;
+    be.sample(tb, SArgs{nullptr, nullptr, nullptr, nullptr, snap->d_config, snap->d_val, snap->seed, L, p, Q,
+                        snap->nper, vmax});
+    return d_out;
   }
 
   // ---- left sweep
@@ -727,7 +799,7 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
 // workspace bytes of every state alone (a chunk of several takes at most the
 // sum), by a dry run per distinct set of bond-sector dims
 inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vector<StateDesc>& desc,
-                                           const std::vector<int>& rows, Want want) {
+                                           const std::vector<int>& rows, Want want, const Snap* snap = nullptr) {
   std::map<std::vector<int>, size_t> seen;
   std::vector<size_t> need(desc.size());
   for (size_t i = 0; i < desc.size(); ++i) {
@@ -737,7 +809,12 @@ inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vecto
       std::vector<Dest> dd;
       Traffic tt;
       Spec sp;
-      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt, want.spec ? &sp : nullptr);
+      Snap sn;
+      if (snap) {
+        sn = *snap;
+        sn.ids = nullptr;
+      }
+      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt, want.spec ? &sp : nullptr, snap ? &sn : nullptr);
       it = seen.emplace(desc[i].dims, cb.bytes).first;
     }
     need[i] = it->second;
@@ -824,7 +901,7 @@ inline size_t compact_desc(int L, int p, int Q, const int* dims, const double* d
       for (int n = 0; n < p && q + n <= Q; ++n) {
         const int r = dims[(k - 1) * Q1 + q], c = dims[k * Q1 + q + n];
         if (r <= 0 || c <= 0) continue;
-        out.blk[(size_t(k) * Q1 + q) * p + n] = Blk{d_data + 2 * off, r, c};
+        out.blk[(size_t(k) * Q1 + q) * p + n] = Blk{d_data ? d_data + 2 * off : nullptr, r, c};  // (null: counting)
         off += size_t(r) * c;
       }
   return off;

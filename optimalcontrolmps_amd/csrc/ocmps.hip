@@ -1805,10 +1805,11 @@ int ocg_get_state(ocg_ctx* c, int which, int t, int* dims, double* data, size_t 
 // free device memory.  Reads the slots only.
 static constexpr size_t kObsKeepBytes = size_t(256) << 20;
 static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so);
-// With so the spectrum stages run too and their results go to *so.
+                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr);
+// With so the spectrum stages run too and their results go to *so; with sn the
+// snapshot launch follows the right sweep instead and its results go to sn's outputs.
 static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                         double* occ_buf, const obs::SpecOutputs* so = nullptr) {
+                         double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
   const OcgParams& P = c->P;
   const int nst = int(slots.size());
   std::vector<obs::StateDesc> desc(nst);
@@ -1842,17 +1843,22 @@ static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0,
         bond[(out0 + i) * (P.L + 1) + b] = sum;
       }
   }
-  return observe_descs(c, desc, out0, o, occ_buf, so);
+  return observe_descs(c, desc, out0, o, occ_buf, so, sn);
 }
 
 // the chunks of observe.hpp's driver over states described on the device
 static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so) {
+                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn) {
   const OcgParams& P = c->P;
   const int nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec) return 0;
+  if (!want.norm && !want.env() && !want.spec && !sn) return 0;
+  if (sn) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
+    if (wo > obs::kSampleMaxOrder) return fail(c, OCG_ECAP, "snapshots: a bond sector above order 512");
+  }
   if (so) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
@@ -1862,12 +1868,15 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     if (wo > obs::kEigMaxOrder) return fail(c, OCG_ECAP, "spectrum: a bond sector above order 512");
   }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want);
+  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want, sn);
   const size_t budget = obs::chunk_budget();
   for (int i0 = 0; i0 < nst;) {
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
+    if (sn && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      return fail(c, OCG_ENOMEM, "snapshots: the workspace of one state (" + std::to_string(sum) +
+                                     " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
@@ -1904,7 +1913,8 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     std::vector<int> status;
     obs::Spec sp;
     if (!rc) {
-      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr);
+      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr, sn);
+      if (sn && be.ok()) be.note(sn->fetch(out0 + i0, S.size(), P.L, c->stream));
       res.resize(2 * std::max<size_t>(dests.size(), 1));
       if (be.ok() && !dests.empty())
         be.note(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost,
@@ -1961,6 +1971,60 @@ static double* observe_prepare(const obs::Outputs& o, size_t n, std::vector<doub
   if (o.occ || !obs::want_of(o).occ) return o.occ;
   tmp.assign(n * o.L * o.p, 0.0);
   return tmp.data();
+}
+
+// the dims of caller-supplied states, before anything is written (wcap >= 0: the
+// bond dimensions must fit it)
+static int staged_check(ocg_ctx* c, int n, const int* dims, int wcap) {
+  const OcgParams& P = c->P;
+  for (int i = 0; i < n; ++i) {
+    const int* d = dims + size_t(i) * P.nsq;
+    for (int j = 0; j < P.nsq; ++j)
+      if (d[j] < 0) return fail(c, OCG_EINVAL, "negative bond dimension");
+    for (int q = 0; q < P.Q1; ++q)
+      if (d[q] != (q == 0 ? 1 : 0) || d[P.L * P.Q1 + q] != (q == P.Q ? 1 : 0))
+        return fail(c, OCG_EINVAL, "bond 0 / bond L must be one state with q = 0 / q = Q");
+    for (int b = 1; b < P.L && wcap >= 0; ++b) {
+      long sum = 0;
+      for (int q = 0; q < P.Q1; ++q) sum += d[size_t(b) * P.Q1 + q];
+      if (sum > wcap) return fail(c, OCG_ECAP, "wcap below the largest bond dimension of the states");
+    }
+  }
+  return 0;
+}
+
+// Caller-supplied states staged a batch at a time in the compact interchange format
+// itself: its blocks are the contiguous row-major matrices the descriptors want, and a
+// sector may be larger than the Schmidt-rank bound of the pool slots (a padded or
+// over-parametrised state).
+static int observe_staged(ocg_ctx* c, int n, const int* dims, const double* const* data, const obs::Outputs& o,
+                          const obs::SpecOutputs* so, obs::Snap* sn, const char* what) {
+  const OcgParams& P = c->P;
+  const int B = std::min(n, 64);
+  for (int i0 = 0; i0 < n; i0 += B) {
+    const int nb = std::min(B, n - i0);
+    std::vector<obs::StateDesc> desc(nb);
+    std::vector<size_t> at(nb + 1, 0);
+    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims + size_t(i0 + i) * P.nsq);
+    double* d_st = nullptr;
+    if (hipMalloc((void**)&d_st, 16 * std::max<size_t>(at[nb], 1)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, OCG_ENOMEM, std::string(what) + ": the staged states do not fit");
+    }
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < nb && e == hipSuccess; ++i) {
+      const int* d = dims + size_t(i0 + i) * P.nsq;
+      if (at[i + 1] > at[i])
+        e = hipMemcpyAsync(d_st + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
+      obs::compact_desc(P.L, P.p, P.Q, d, d_st + 2 * at[i], desc[i]);
+    }
+    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, so, sn)
+                             : fail(c, OCG_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d_st);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 extern "C" {
@@ -2048,47 +2112,116 @@ int ocg_observe_spectrum_states(ocg_ctx* c, int n, const int* dims, const double
   const OcgParams& P = c->P;
   const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, P.L, P.p, 0, nullptr};
   const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-  for (int i = 0; i < n; ++i) {  // before anything is written
-    const int* d = dims + size_t(i) * P.nsq;
-    for (int j = 0; j < P.nsq; ++j)
-      if (d[j] < 0) return fail(c, OCG_EINVAL, "negative bond dimension");
-    for (int q = 0; q < P.Q1; ++q)
-      if (d[q] != (q == 0 ? 1 : 0) || d[P.L * P.Q1 + q] != (q == P.Q ? 1 : 0))
-        return fail(c, OCG_EINVAL, "bond 0 / bond L must be one state with q = 0 / q = Q");
-    for (int b = 1; b < P.L && so.weights(); ++b) {
-      long sum = 0;
-      for (int q = 0; q < P.Q1; ++q) sum += d[size_t(b) * P.Q1 + q];
-      if (sum > wcap) return fail(c, OCG_ECAP, "wcap below the largest bond dimension of the states");
-    }
-  }
-  // Staged a batch at a time in the compact interchange format itself: its blocks are
-  // the contiguous row-major matrices the descriptors want, and a sector may be larger
-  // than the Schmidt-rank bound of the pool slots (a padded or over-parametrised state).
-  const int B = std::min(n, 64);
-  for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb = std::min(B, n - i0);
-    std::vector<obs::StateDesc> desc(nb);
-    std::vector<size_t> at(nb + 1, 0);
-    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims + size_t(i0 + i) * P.nsq);
-    double* d_st = nullptr;
-    if (hipMalloc((void**)&d_st, 16 * std::max<size_t>(at[nb], 1)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(c, OCG_ENOMEM, "spectrum: the staged states do not fit");
-    }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < nb && e == hipSuccess; ++i) {
-      const int* d = dims + size_t(i0 + i) * P.nsq;
-      if (at[i + 1] > at[i])
-        e = hipMemcpyAsync(d_st + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
-      obs::compact_desc(P.L, P.p, P.Q, d, d_st + 2 * at[i], desc[i]);
-    }
-    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, &so)
-                             : fail(c, OCG_EHIP, std::string("spectrum: ") + hipGetErrorString(e));
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_st);
-    if (rc) return rc;
+  if (int rc = staged_check(c, n, dims, so.weights() ? std::max(wcap, 0) : -1)) return rc;
+  return observe_staged(c, n, dims, data, o, &so, nullptr, "spectrum");
+}
+
+// the trajectory slots of a request (which / ts as ocg_observe)
+static int trajectory_slots(ocg_ctx* c, int which, const int* ts, int nt, std::vector<int>& slots,
+                            std::vector<unsigned long long>* ids) {
+  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
+  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
+  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
+  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
+  slots.resize(nt);
+  if (ids) ids->resize(nt);
+  for (int i = 0; i < nt; ++i) {
+    const int t = ts ? ts[i] : i;
+    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
+    slots[i] = base + t;
+    if (ids) (*ids)[i] = (unsigned long long)t;
   }
   return 0;
+}
+
+int ocg_sample(ocg_ctx* c, int which, const int* ts, int nt, int nshots, unsigned long long seed, signed char* config,
+               double* logp) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_sample(c->hbm, which, ts, nt, nshots, seed, config, logp));
+  if (nshots < 0 || (nshots > 0 && nt > 0 && !config)) return fail(c, OCG_EINVAL, "bad shots / outputs");
+  std::vector<int> slots;
+  std::vector<unsigned long long> ids;
+  if (int rc = trajectory_slots(c, which, ts, nt, slots, &ids)) return rc;
+  if (nt == 0 || nshots == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  obs::Snap sn;
+  sn.nper = nshots;
+  sn.seed = seed;
+  sn.ids = ids.data();
+  sn.config = config;
+  sn.val = logp;
+  return observe_slots(c, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+}
+
+int ocg_sample_states(ocg_ctx* c, int n, const int* dims, const double* const* data, int nshots,
+                      unsigned long long seed, signed char* config, double* logp) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_sample_states(c->hbm, n, dims, data, nshots, seed, config, logp));
+  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
+  if (nshots < 0 || (nshots > 0 && n > 0 && !config)) return fail(c, OCG_EINVAL, "bad shots / outputs");
+  if (n == 0 || nshots == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = staged_check(c, n, dims, -1)) return rc;
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  std::vector<unsigned long long> ids(n);
+  for (int i = 0; i < n; ++i) ids[i] = (unsigned long long)i;
+  obs::Snap sn;
+  sn.nper = nshots;
+  sn.seed = seed;
+  sn.ids = ids.data();
+  sn.config = config;
+  sn.val = logp;
+  return observe_staged(c, n, dims, data, o, nullptr, &sn, "snapshots");
+}
+
+// every configuration has entries in 0..p-1 that add up to Q
+static int check_configs(ocg_ctx* c, const signed char* configs, int nconf, double* amp) {
+  if (nconf < 0 || (nconf > 0 && (!configs || !amp))) return fail(c, OCG_EINVAL, "bad configurations / outputs");
+  for (int j = 0; j < nconf; ++j) {
+    int sum = 0;
+    for (int k = 0; k < c->P.L; ++k) {
+      const int v = configs[size_t(j) * c->P.L + k];
+      if (v < 0 || v >= c->P.p) return fail(c, OCG_EINVAL, "a configuration entry outside 0..p-1");
+      sum += v;
+    }
+    if (sum != c->P.Q) return fail(c, OCG_EINVAL, "a configuration that does not hold Q particles");
+  }
+  return 0;
+}
+
+int ocg_fock_amplitudes(ocg_ctx* c, int which, const int* ts, int nt, const signed char* configs, int nconf,
+                        double* amp) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_fock_amplitudes(c->hbm, which, ts, nt, configs, nconf, amp));
+  std::vector<int> slots;
+  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
+  if (int rc = check_configs(c, configs, nconf, amp)) return rc;
+  if (nt == 0 || nconf == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  obs::Snap sn;
+  sn.nper = nconf;
+  sn.given = configs;
+  sn.val = amp;
+  return observe_slots(c, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+}
+
+int ocg_fock_amplitudes_states(ocg_ctx* c, int n, const int* dims, const double* const* data,
+                               const signed char* configs, int nconf, double* amp) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_fock_amplitudes_states(c->hbm, n, dims, data, configs, nconf, amp));
+  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
+  if (int rc = check_configs(c, configs, nconf, amp)) return rc;
+  if (n == 0 || nconf == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = staged_check(c, n, dims, -1)) return rc;
+  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  obs::Snap sn;
+  sn.nper = nconf;
+  sn.given = configs;
+  sn.val = amp;
+  return observe_staged(c, n, dims, data, o, nullptr, &sn, "amplitudes");
 }
 
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,

@@ -323,6 +323,42 @@ class GpuTDMRG::Engine {
                   c, "ocg_observe_spectrum");
     return o;
   }
+  // Fock-state snapshots of the device-resident trajectory (ocg_sample): nshots
+  // occupation configurations of each state ts (empty: all N) drawn from
+  // |<n|s>|^2 / <s|s>, with their log-probabilities.  The random numbers depend on
+  // (seed, t, shot, site) alone; which is not mixed in.
+  TrajectorySnapshots sample(int which, const std::vector<int>& ts, int nshots, unsigned long long seed) {
+    TrajectorySnapshots o;
+    o.L = stepper.L;
+    o.nshots = nshots < 0 ? 0 : nshots;
+    o.ts = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) o.ts.push_back(int(t));
+    const size_t nt = o.ts.size();
+    o.configs.assign(nt * o.nshots * o.L, (signed char)-1);
+    o.logps.assign(nt * o.nshots, 0.0);
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_sample(c, which, o.ts.data(), int(nt), nshots, seed, o.configs.data(), o.logps.data()), c,
+                  "ocg_sample");
+    return o;
+  }
+  // <n|s> of the configurations (nconf x L occupations, row after row) for the
+  // states ts (empty: all N) of the device-resident trajectory (ocg_fock_amplitudes):
+  // [e][conf], raw (not divided by the norm).
+  std::vector<Cplx> fockAmplitudes(int which, const std::vector<int>& ts, const std::vector<signed char>& configs) {
+    std::vector<int> tt = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) tt.push_back(int(t));
+    const size_t nconf = configs.size() / size_t(stepper.L);
+    if (nconf * size_t(stepper.L) != configs.size())
+      throw std::invalid_argument("fockAmplitudes: configs is not a multiple of L long");
+    std::vector<Cplx> amp(tt.size() * nconf, Cplx(0, 0));
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_fock_amplitudes(c, which, tt.data(), int(tt.size()), configs.data(), int(nconf),
+                                      reinterpret_cast<double*>(amp.data())),
+                  c, "ocg_fock_amplitudes");
+    return amp;
+  }
   std::vector<MPS> psiTrajectory() {
     std::vector<MPS> out;
     for (size_t t = 0; t < N; ++t)

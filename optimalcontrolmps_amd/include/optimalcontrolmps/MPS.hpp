@@ -110,4 +110,20 @@ struct TrajectoryObservables {
   }
 };
 
+// Fock-state snapshots of nt trajectory states drawn on the device (ocg_sample,
+// include/ocmps.h): what GpuTDMRG::Engine::sample, OptimalControl::samplePsit and
+// the host sampleFock (correlations.hpp) return.  Entry e belongs to trajectory
+// state ts[e]; a shot of a zero state has -1 at every site and logp = -inf.
+struct TrajectorySnapshots {
+  int L = 0, nshots = 0;
+  std::vector<int> ts;               // [e] state index (the id mixed into the random numbers)
+  std::vector<signed char> configs;  // [e][shot][L] occupations
+  std::vector<double> logps;         // [e][shot] ln(|<n|psi>|^2 / <psi|psi>)
+  size_t size() const { return ts.size(); }
+  int shots() const { return nshots; }
+  // occupation of site k = 1..L in shot s of entry e
+  int config(size_t e, int s, int k) const { return configs[(e * nshots + s) * L + (k - 1)]; }
+  double logp(size_t e, int s) const { return logps[e * nshots + s]; }
+};
+
 }  // namespace ocmps

@@ -14,6 +14,8 @@
 //           hessianFresh(u, F&, divT&, H) (all of the above for a new control), psiTrajectory(),
 //           observe(which, ts, rows), observeSpectrum(which, ts, weights) (optional: getPsitObservables
 //           needs the first, and the second when entropies are asked for),
+//           sample(which, ts, nshots, seed), fockAmplitudes(which, ts, configs) (optional: samplePsit,
+//           getPsitFockProbability),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -69,6 +71,23 @@ class OptimalControl {
     ocmps::TrajectoryObservables o = engine->observe(0, ts, rows);
     if (entropy) o.entropy = engine->observeSpectrum(0, ts, false).entropy;
     return o;
+  }
+  // Projective occupation snapshots of psi_t for t in ts (empty: all), drawn on
+  // the device (Engine::sample; the host counterpart for one state is sampleFock of
+  // correlations.hpp, with the same random numbers): what a quantum-gas
+  // microscope records.  Only for steppers whose Engine has sample() (GpuTDMRG).
+  ocmps::TrajectorySnapshots samplePsit(const std::vector<int>& ts, int nshots, unsigned long long seed) const {
+    return engine->sample(0, ts, nshots, seed);
+  }
+  // |<config|psi_t>|^2 / <psi_t|psi_t> for t in ts (empty: all), e.g. the
+  // Mott-state probability along the ramp (Engine::fockAmplitudes + the norms of observe()).
+  stdvec getPsitFockProbability(const std::vector<int>& ts, const std::vector<int>& config) const {
+    const std::vector<signed char> cf(config.begin(), config.end());
+    const std::vector<Cplx> amp = engine->fockAmplitudes(0, ts, cf);
+    const ocmps::TrajectoryObservables o = engine->observe(0, ts, {});
+    stdvec pr(amp.size());
+    for (size_t e = 0; e < amp.size(); ++e) pr[e] = o.norm2[e] > 0 ? std::norm(amp[e]) / o.norm2[e] : 0.0;
+    return pr;
   }
   size_t getM() const { return M; }
   size_t getN() const { return N; }

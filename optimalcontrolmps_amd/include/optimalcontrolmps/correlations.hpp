@@ -428,4 +428,86 @@ inline std::vector<double> entanglementEntropy(const BoseHubbard& /*sites*/, con
   return S;
 }
 
+// ---- Fock-state snapshots of one host state: the algorithm and the
+// counter-based random numbers of ocg_sample (include/ocmps.h), so that a host
+// state and the same state on the device give the same shots (up to a decision
+// that rounding puts on the other side of a CDF boundary).  id takes the place
+// of the state index t.  The path the device call replaces.
+namespace obs {
+inline unsigned long long sampleMix(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+}  // namespace obs
+
+inline TrajectorySnapshots sampleFock(const MPS& psi, int nshots, unsigned long long seed, int id = 0) {
+  TrajectorySnapshots o;
+  o.L = psi.L;
+  o.nshots = nshots < 0 ? 0 : nshots;
+  o.ts = {id};
+  o.configs.assign(size_t(o.nshots) * psi.L, (signed char)-1);
+  o.logps.assign(size_t(o.nshots), -HUGE_VAL);
+  const obs::Dense D = obs::dense(psi);
+  const obs::Envs V = obs::envs(D);  // Renv[b][c'][c] = the transpose of ocg_observe's Renv_b
+  const int L = psi.L, p = psi.p, Q = psi.Q;
+  const double norm2 = V.Renv[0][0].real();
+  const unsigned long long hi = obs::sampleMix(obs::sampleMix(seed) ^ (unsigned long long)id);
+  std::vector<double> pr(p), cs(p);
+  std::vector<obs::cmat> w(p);
+  for (int s = 0; s < o.nshots; ++s) {
+    const unsigned long long hs = obs::sampleMix(hi ^ (unsigned long long)s);
+    obs::cmat v(1, Cplx(1, 0));  // the row vector over sector q of bond k - 1
+    int q = 0;
+    bool dead = false;
+    for (int k = 1; k <= L && !dead; ++k) {
+      const int cr = D.chi[k], a0 = D.off[k - 1][q], r = int(v.size());
+      const obs::cmat& A = D.A[k];
+      double run = 0;
+      for (int n = 0; n < p; ++n) {
+        pr[n] = 0;
+        w[n].clear();
+        const int c = q + n <= Q ? psi.dim(k, q + n) : 0;
+        if (c > 0) {
+          const int c0 = D.off[k][q + n];
+          w[n].assign(c, Cplx(0, 0));
+          for (int a = 0; a < r; ++a)
+            for (int x = 0; x < c; ++x) w[n][x] += v[a] * A[(size_t(a0 + a) * p + n) * cr + c0 + x];
+          const obs::cmat& R = V.Renv[k];
+          Cplx acc = 0;
+          for (int y = 0; y < c; ++y) {  // y: the bra index of Renv
+            Cplx t = 0;
+            for (int x = 0; x < c; ++x) t += w[n][x] * R[size_t(c0 + y) * cr + c0 + x];
+            acc += t * std::conj(w[n][y]);
+          }
+          pr[n] = acc.real() > 0 ? acc.real() : 0.0;
+        }
+        run += pr[n];
+        cs[n] = run;
+      }
+      if (!(run > 0)) {
+        dead = true;
+        break;
+      }
+      const double u = double(obs::sampleMix(hs ^ (unsigned long long)k) >> 11) * 0x1.0p-53;
+      int pick = -1, last = -1;
+      for (int n = 0; n < p; ++n) {
+        if (pr[n] > 0) last = n;
+        if (pick < 0 && u * run < cs[n]) pick = n;
+      }
+      if (pick < 0) pick = last;
+      o.configs[size_t(s) * L + (k - 1)] = (signed char)pick;
+      v = w[pick];
+      q += pick;
+    }
+    if (dead) {
+      for (int k = 0; k < L; ++k) o.configs[size_t(s) * L + k] = (signed char)-1;
+      continue;
+    }
+    o.logps[s] = std::log(std::norm(v[0])) - std::log(norm2);
+  }
+  return o;
+}
+
 }  // namespace ocmps

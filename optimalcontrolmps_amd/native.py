@@ -45,9 +45,9 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
                   "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
-                  "observe_eig.hpp"],
+                  "observe_eig.hpp", "observe_sample.hpp"],
         "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
-                "observe_eig.hpp"],
+                "observe_eig.hpp", "observe_sample.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -78,6 +78,7 @@ _lib = None
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int)
 szp = C.POINTER(C.c_size_t)
+bp = C.POINTER(C.c_byte)
 
 
 class OcgInfo(C.Structure):
@@ -131,6 +132,10 @@ SIGNATURES = [
     ("ocg_observe_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), ip, C.c_int, dp, dp, ip, dp, dp]),
     ("ocg_observe_spectrum", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.c_int, dp, dp, ip]),
     ("ocg_observe_spectrum_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), C.c_int, dp, dp, ip]),
+    ("ocg_sample", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.c_int, C.c_ulonglong, bp, dp]),
+    ("ocg_sample_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), C.c_int, C.c_ulonglong, bp, dp]),
+    ("ocg_fock_amplitudes", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, bp, C.c_int, dp]),
+    ("ocg_fock_amplitudes_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), bp, C.c_int, dp]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -540,6 +545,67 @@ class Engine:
         data = (dp * n)(*[r.ctypes.data_as(dp) for r in raws])
         self._chk(lib().ocg_observe_spectrum_states(self.h, n, dims.ctypes.data_as(ip), data, wcap, *ptrs),
                   "ocg_observe_spectrum_states")
+        return out
+
+    def _staged(self, states):
+        n = len(states)
+        dims = np.ascontiguousarray(np.concatenate([m.dims for m in states]).astype(np.int32))
+        raws = [np.ascontiguousarray(m.raw()) for m in states]
+        return dims, raws, (dp * n)(*[r.ctypes.data_as(dp) for r in raws])
+
+    def sample(self, which=0, ts=None, nshots=1, seed=0, logp=True):
+        """Fock-state snapshots of the device trajectory states (ocg_sample): which / ts
+        as observe().  Returns dict(config int8 (nt, nshots, L), logp (nt, nshots)):
+        nshots occupation configurations per state drawn from |<n|s>|^2 / <s|s> and the
+        log-probability of each.  The random numbers depend on (seed, t, shot, site)
+        alone: a state's shots do not depend on what else is requested, and which is not
+        mixed in.  A zero state gives -1 everywhere and logp = -inf.  logp=False skips
+        that output."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        nshots = int(nshots)
+        out = {"config": np.zeros((len(tt), max(nshots, 0), self.L), np.int8)}
+        if logp:
+            out["logp"] = np.zeros((len(tt), max(nshots, 0)))
+        self._chk(lib().ocg_sample(self.h, int(which), pt, len(tt), nshots, int(seed) & (2 ** 64 - 1),
+                                   out["config"].ctypes.data_as(bp),
+                                   out["logp"].ctypes.data_as(dp) if logp else None), "ocg_sample")
+        return out
+
+    def sample_states(self, states, nshots=1, seed=0, logp=True):
+        """sample() for caller-supplied host states of any gauge or norm (ocg_sample_states);
+        the position of a state in the list takes the place of t in the random numbers."""
+        n, nshots = len(states), int(nshots)
+        out = {"config": np.zeros((n, max(nshots, 0), self.L), np.int8)}
+        if logp:
+            out["logp"] = np.zeros((n, max(nshots, 0)))
+        if n == 0:
+            return out
+        dims, raws, data = self._staged(states)
+        self._chk(lib().ocg_sample_states(self.h, n, dims.ctypes.data_as(ip), data, nshots, int(seed) & (2 ** 64 - 1),
+                                          out["config"].ctypes.data_as(bp),
+                                          out["logp"].ctypes.data_as(dp) if logp else None), "ocg_sample_states")
+        return out
+
+    def fock_amplitudes(self, which=0, ts=None, configs=()):
+        """<n|s> of the configurations configs (nconf, L) for the device trajectory states
+        (ocg_fock_amplitudes): complex (nt, nconf), raw (sum over all n of |amp|^2 = norm2)."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        cf = np.ascontiguousarray(np.asarray(configs, np.int8).reshape(-1, self.L))
+        out = np.zeros((len(tt), len(cf)), np.complex128)
+        self._chk(lib().ocg_fock_amplitudes(self.h, int(which), pt, len(tt), cf.ctypes.data_as(bp), len(cf),
+                                            out.ctypes.data_as(dp)), "ocg_fock_amplitudes")
+        return out
+
+    def fock_amplitudes_states(self, states, configs=()):
+        """fock_amplitudes() for caller-supplied host states (ocg_fock_amplitudes_states)."""
+        n = len(states)
+        cf = np.ascontiguousarray(np.asarray(configs, np.int8).reshape(-1, self.L))
+        out = np.zeros((n, len(cf)), np.complex128)
+        if n == 0:
+            return out
+        dims, raws, data = self._staged(states)
+        self._chk(lib().ocg_fock_amplitudes_states(self.h, n, dims.ctypes.data_as(ip), data, cf.ctypes.data_as(bp),
+                                                   len(cf), out.ctypes.data_as(dp)), "ocg_fock_amplitudes_states")
         return out
 
     def stats(self, kind):

@@ -2,7 +2,7 @@
 was before: one ocg_get_state copy per state (a lower bound of that path, which
 adds the host contraction of correlations.hpp on top).
 
-    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|all] [--reps R] [--out DIR]
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|all] [--reps R] [--out DIR]
 
 One process; every shape is warmed up; each timed call ends in a device
 synchronise (both entry points return only after their results are on the
@@ -18,6 +18,13 @@ the path they replace is that loop plus N_t times the host
 entanglementEntropy(sites, psi) of one mid-trajectory state, timed by a small
 stand-alone program.  Writes observe_spectrum_config1.json /
 observe_spectrum_config4.json.
+
+p1 / p4: Fock-state snapshots (ocg_sample, 1024 shots of every state) and the
+Mott-state amplitude (ocg_fock_amplitudes) at the same two shapes, alternating
+with the copy loop; the path they replace is that loop plus N_t times the host
+sampleFock(psi, 1024, seed, t) of one mid-trajectory state, timed on one thread by
+a small stand-alone program.  Writes observe_sample_config1.json /
+observe_sample_config4.json.
 """
 from __future__ import annotations
 
@@ -88,7 +95,7 @@ def config1(reps):
     return res
 
 
-def host_expectation_seconds(state, tool="host_expectation_timing"):
+def host_expectation_seconds(state, tool="host_expectation_timing", args=()):
     """copy-free part of the old path for one state: expectationValues(sites, psi, "N") (or, with
     tool="host_entropy_timing", entanglementEntropy(sites, psi)) on the host"""
     src = os.path.join(native.PKG_DIR, "tools", tool + ".cpp")
@@ -99,7 +106,8 @@ def host_expectation_seconds(state, tool="host_expectation_timing"):
         with open(path, "wb") as f:
             f.write(np.array([state.L, state.p, state.Q, state.dims.size, state.data.size], np.int32).tobytes())
             f.write(state.dims.tobytes() + state.data.tobytes())
-        return json.loads(subprocess.run([exe, path], capture_output=True, text=True, check=True).stdout)
+        return json.loads(subprocess.run([exe, path] + [str(a) for a in args], capture_output=True, text=True,
+                                         check=True).stdout)
 
 
 def config4(reps):
@@ -202,19 +210,83 @@ def spectrum4(reps):
     return res
 
 
+def sample_cases(eng, Nt, reps, warm, nshots=1024):
+    """snapshots (nshots of every state), the Mott amplitude of every state, the environments alone (observe
+    occ) and the copy loop, alternating; kind 9 (and kind 7) of the snapshot call from a pass of its own"""
+    dims = np.zeros((eng.L + 1) * (eng.Q + 1), np.int32)
+    data = np.zeros(2 * eng.cap)
+    mott = [[1] * eng.L]
+    cases = {"sample": lambda: eng.sample(0, None, nshots, 1),
+             "fock_amplitude_mott": lambda: eng.fock_amplitudes(0, None, mott),
+             "observe_occ": lambda: eng.observe(0, None, (), outputs=("occ",)),
+             "get_state_copies": lambda: copy_all(eng, 0, Nt, dims, data)}
+    for f in cases.values():
+        for _ in range(warm):
+            f()
+    t = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    res = {"nshots": nshots}
+    res.update({k: spread(v) for k, v in t.items()})
+    for k in ("sample", "observe_occ"):
+        eng.reset_stats()
+        cases[k]()
+        res[k + "_kind9"] = eng.stats(9)
+        res[k + "_kind7_ms"] = eng.stats(7)["ms"]
+    host = host_expectation_seconds(eng.state(0, Nt // 2), "host_sample_timing", (nshots,))
+    res["host_sampleFock_one_state"] = host
+    old = res["get_state_copies"]["median_ms"] + Nt * 1e3 * host["seconds"]   # (the call forms its environments)
+    res["old_path_ms"] = old
+    res["sample_vs_old_path"] = old / res["sample"]["median_ms"]
+    res["sample_vs_copies"] = res["get_state_copies"]["median_ms"] / res["sample"]["median_ms"]
+    res["shots_per_second"] = Nt * nshots / (1e-3 * res["sample"]["median_ms"])
+    return res
+
+
+def sample1(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    eng.propagate(np.linspace(2.5, 50.0, Nt), 1)
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine (no k_gemm: kind 7 is 0), 1024 shots per state",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1)))}
+    res.update(sample_cases(eng, Nt, reps, 2))
+    return res
+
+
+def sample4(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 20, 7, 20, 1.0, 0.005, 1e-8, 256, 33
+    z = np.load(os.path.join(GOLDEN, "c4_warm256.npz"), allow_pickle=False)
+    c4 = np.load(os.path.join(GOLDEN, "c4.npz"), allow_pickle=False)
+    u = np.load(os.path.join(GOLDEN, "c4_w256h33.npz"), allow_pickle=False)["u"]
+    eng = Engine(L, p, Q, J, dt, cut, maxm, engine="hbm")
+    eng.set_states(MPS(L, p, Q, c4["w256h/tgt_dims"], c4["w256h/tgt_data"]), MPS(L, p, Q, z["dims"], z["data"]))
+    eng.propagate(u, 1)
+    res = {"config": "4 slice: L=20 p=7 Q=20 chi=256 (warm state) N_t=33, HBM engine, 1024 shots per state",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1)))}
+    res.update(sample_cases(eng, Nt, reps, 1))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "all"])
+    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4)),
-                           ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4))):
+                           ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4)),
+                           ("p1", sample1, a.reps), ("p4", sample4, max(3, a.reps // 4))):
         if a.config in (name, "all"):
             res = fn(reps)
             res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
-            out = f"observe_spectrum_config{name[1:]}.json" if name.startswith("s") else f"observe_config{name}.json"
+            kind = {"s": "observe_spectrum_config", "p": "observe_sample_config"}.get(name[0], "observe_config")
+            out = f"{kind}{name[-1]}.json"
             with open(os.path.join(a.out, out), "w") as f:
                 json.dump(res, f, indent=1)
             print(json.dumps(res))
