@@ -266,8 +266,10 @@ struct Engine {
   // shifts per thread and multisection round (EProb::ks): 1 = bisection (default), 4 = round 5's
   int bisect_ks = std::getenv("OCG_HBM_BISECT_KS") && std::atoi(std::getenv("OCG_HBM_BISECT_KS")) == 4 ? 4 : 1;
   long split_launches = 0, split_blocks = 0;
-  // the split runs while its workgroups number at most split_max_wg per CU (OCG_HBM_SPLIT_WG)
-  int split_max_wg = std::getenv("OCG_HBM_SPLIT_WG") ? std::atoi(std::getenv("OCG_HBM_SPLIT_WG")) : 2;
+  // OCG_HBM_SPLIT_WG=w > 0 (A/B runs only): a launch whose split workgroups number more than w
+  // per CU keeps the in-kernel multisection for all its blocks.  A block's bits then depend on
+  // its launch mates, which voids every bitwise guarantee between batchings; 0 (default): off
+  int split_max_wg = std::getenv("OCG_HBM_SPLIT_WG") ? std::atoi(std::getenv("OCG_HBM_SPLIT_WG")) : 0;
   double phase_ms[8] = {0};
   long phase_n[8] = {0};
   double steps_done[8] = {0};
@@ -942,10 +944,14 @@ struct Engine {
       }
     }
     // large register-path blocks: the tridiagonal in k_heev_vals_any, the
-    // eigenvalues split over workgroups (k_heev_bisect_split) right after it
-    // Only while the split's workgroups fit about two per CU: a launch with many
-    // large blocks (the full-horizon row batches) already fills the GPU, and the
-    // split's g threads per eigenvalue would only add Sturm work there.
+    // eigenvalues split over workgroups (k_heev_bisect_split) right after it.
+    // Which of the two multisections a block takes depends on the block and on
+    // context settings only, never on the rest of its launch: they converge to
+    // different final intervals (different bits), and pipelined == stored,
+    // checkpointed == stored and sharded == full rest on batch independence.
+    // (A launch with many large blocks, as the full horizon's row batches,
+    // fills the GPU already and the split's g threads per eigenvalue only add
+    // Sturm work there; OCG_HBM_SPLIT_WG trades the guarantee for that.)
     std::vector<int> split;
     int max_split = 0;
     if (!thresh_on && split_min > 0) {
@@ -960,7 +966,7 @@ struct Engine {
           ntask += (n + split_spe - 1) / split_spe;
         }
       }
-      if (ntask > long(split_max_wg) * n_cu) split.clear();
+      if (split_max_wg > 0 && ntask > long(split_max_wg) * n_cu) split.clear();
       for (int i : split) R.probs[i].defer = 1;
     }
     R.d_probs = upload(R.probs);

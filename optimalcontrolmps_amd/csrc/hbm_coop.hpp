@@ -507,7 +507,10 @@ __global__ __launch_bounds__(CPT, 1) void k_heev_vals_coop(const EProb* __restri
           p = zsub(p, zadd(zmul(pu[q], dw), zmul(pw[q], du)));
         }
       }
-      const double K = 0.5 * t * t * (uau.x - 2.0 * sd);
+      // t = 2 / |u|^2: t^2 overflows for a column of norm below ~1e-77 (the trailing columns of
+      // a Gram block of norm ~1e-60), while t (t x) stays in range; same bits wherever t^2 is finite
+      const double ht2 = 0.5 * t * t, uu = uau.x - 2.0 * sd;
+      const double K = ht2 <= 1.7976931348623157e308 ? ht2 * uu : 0.5 * t * (t * uu);
       rw = zsub(zsc(p1, t), zsc(u0, K));
       ru = u0;
       if (live) {

@@ -1336,7 +1336,11 @@ __global__ __launch_bounds__(VNT) void k_heev_vecs_reg(const EProb* __restrict__
 #endif
   double* Z = fast ? Zl : P.Z;
   const int lz = fast ? ldz : n;
-  if (fast) {
+  if (tn == 0.0) {
+    // the zero block (a decomposition of total weight 0 keeps one state): every unit vector is an
+    // eigenvector, and inverse iteration would divide by the `tiny` pivot floor until it overflows
+    for (int e = tid; e < n * k; e += VNT) Z[(size_t)(e / k) * lz + e % k] = e / k == e % k ? 1.0 : 0.0;
+  } else if (fast) {
     // pivots in the region's tail after Z: as many eigenvectors per batch as fit (all of them when k <= 64
     // and n (k + 1 + k) doubles fit)
     double* piv = Zl + (size_t)n * ldz;

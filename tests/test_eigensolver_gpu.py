@@ -16,34 +16,11 @@ tests at Maxm 16/32 never reach them.  Checked per block, all gauge-invariant:
 import numpy as np
 import pytest
 
-import oracle_ffi as O
+from decomp_reference import block, check
 
 pytestmark = pytest.mark.gpu
 
 L, p, NPART = 20, 7, 20   # an HBM-engine context (the chain shape does not enter)
-
-
-def block(rng, n, c, spec, rank=None):
-    """n x c complex with singular values spec (length min(n, c) or rank)"""
-    r = len(spec) if rank is None else rank
-    U, _ = np.linalg.qr(rng.normal(size=(n, r)) + 1j * rng.normal(size=(n, r)))
-    V, _ = np.linalg.qr(rng.normal(size=(c, r)) + 1j * rng.normal(size=(c, r)))
-    return (U * np.asarray(spec[:r])) @ V.conj().T
-
-
-def check(M, res, cutoff, maxm):
-    k, w, A, B = res
-    s = np.linalg.svd(M, compute_uv=False)
-    lam = s ** 2
-    k_ref = O.truncate(lam, cutoff, maxm)
-    assert k == k_ref, (M.shape, k, k_ref)
-    # resolved eigenvalues (the kept ones and every one above the unresolved threshold)
-    wd = np.sort(w)[::-1]
-    assert np.abs(wd[:k] - lam[:k]).max() <= 1e-12 * lam[0], M.shape
-    assert np.abs(A.conj().T @ A - np.eye(k)).max() <= 1e-11, M.shape
-    U, s2, Vh = np.linalg.svd(M, full_matrices=False)
-    Mk = (U[:, :k] * s2[:k]) @ Vh[:k]
-    assert np.linalg.norm(A @ B - Mk) <= 1e-9 * np.linalg.norm(M), M.shape
 
 
 @pytest.fixture(scope="module")
