@@ -83,8 +83,9 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * 3 ocg_get_info_sz, ocg_get_path_stats, ocg_abi_version (round 6);
  * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9;
  * 5 ocg_observe_spectrum, ocg_observe_spectrum_states;
- * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states. */
-#define OCG_ABI_VERSION 6
+ * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states;
+ * 7 ocg_observe_moments, ocg_observe_moments_states. */
+#define OCG_ABI_VERSION 7
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
 int ocg_set_tstep(ocg_ctx* ctx, double tstep);
@@ -318,6 +319,32 @@ int ocg_fock_amplitudes(ocg_ctx* ctx, int which, const int* ts, int nt, const si
 int ocg_fock_amplitudes_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data,
                                const signed char* configs, int nconf, double* amp);
 
+/* Energy moments of stored states.  With H(J, U) = -J K + U D,
+ * K = sum_{i<L} (a+_i a_{i+1} + a_i a+_{i+1}) (a, a+ cut at p levels, as the
+ * gates) and D = sum_i n_i (n_i - 1) / 2 (the dH of the context), state s gives
+ *   mom[7] = { norm2 = <s|s>, k1 = <s|K|s>, d1 = <s|D|s>, kk = <s|K K|s>,
+ *              dd = <s|D D|s>, kd_re, kd_im = <s|K D|s> }
+ * raw (none divided by norm2) and independent of J and U, so that for any (J, U)
+ *   E = (-J k1 + U d1) / norm2,
+ *   Var = (J^2 kk - 2 J U kd_re + U^2 dd) / norm2 - E^2,
+ *   d<D>/dt = -2 J kd_im / norm2 (hbar = 1).
+ * A left-to-right sweep of the environments of the operator automaton (0 nothing
+ * yet, 1 a+ placed, 2 a placed, 3 a K term done, 4 a D term done) for the left and
+ * the right operator of each product: no right environments, so the centre may sit
+ * anywhere and the state need not be normalised.  A state without a surviving path
+ * gives zeros.  which / ts / existence rules and chunking as ocg_observe
+ * (OCG_ENOMEM if one state's workspace exceeds the chunk budget); bond sectors of
+ * order up to 512 (OCG_ECAP above).  States whose sectors are all at most 16 wide
+ * (in a context with Q <= 244) run in one kernel per chunk (OCG_OBS_ENERGY_CHAIN=0: the task-list path for
+ * all; the two agree to rounding, not bit for bit).  A state's numbers depend on
+ * the state and its path alone: bit-identical whatever else is requested and
+ * however the request is chunked.  mom[nt][7]; nt == 0 writes nothing.  Reads the
+ * trajectories only. */
+int ocg_observe_moments(ocg_ctx* ctx, int which, const int* ts, int nt, double* mom);
+/* The same for n caller-supplied host states (as ocg_observe_spectrum_states: any
+ * gauge or norm, zero-padded sectors allowed), staged on the device in batches. */
+int ocg_observe_moments_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, double* mom);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -353,7 +380,7 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
  * segment length of the last one), 9 the observable kernels of ocg_observe /
  * ocg_observe_states / ocg_observe_spectrum[_states] / ocg_sample[_states] /
- * ocg_fock_amplitudes[_states] (HIP-event time of their chunks, kernel launches, and the
+ * ocg_fock_amplitudes[_states] / ocg_observe_moments[_states] (HIP-event time of their chunks, kernel launches, and the
  * algorithmic bytes and flops of the host-built task lists).  Sums since the
  * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,

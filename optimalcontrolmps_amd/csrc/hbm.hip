@@ -3206,6 +3206,9 @@ struct ObsBackend {
   void sample(obs::SampleTable& tb, const obs::SArgs& a) {
     HCK(obs::sample_launch(tb, a, E.st, [&](auto& v) { return E.upload(v); }));
   }
+  void energy(obs::EnergyTable& tb, const obs::EArgs& a, std::vector<double>& coef) {
+    HCK(obs::energy_launch(tb, a, coef, E.st, [&](auto& v) { return E.upload(v); }));
+  }
 };
 
 obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
@@ -3252,11 +3255,16 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
   const int L = E.L, nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !sn) return;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !sn) return;
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
     if (wo > obs::kSampleMaxOrder) throw hbm::Error(2, "snapshots: a bond sector above order 512");
+  }
+  if (want.mom) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
+    if (wo > obs::kEnergyMaxOrder) throw hbm::Error(2, "moments: a bond sector above order 512");
   }
   if (so) {
     int wb = 0, wo = 0;
@@ -3273,9 +3281,9 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if (sn && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      throw hbm::Error(6, "snapshots: the workspace of one state (" + std::to_string(sum) +
-                              " B) exceeds the chunk budget");
+    if ((sn || want.mom) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      throw hbm::Error(6, std::string(sn ? "snapshots" : "moments") + ": the workspace of one state (" +
+                              std::to_string(sum) + " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
@@ -3592,6 +3600,30 @@ int hbm_fock_amplitudes_states(hbm_engine* h, int n, const int* dims, const doub
     sn.given = configs;
     sn.val = amp;
     observe_staged(h, n, dims, data, o, nullptr, &sn);
+  });
+}
+
+int hbm_observe_moments(hbm_engine* h, int which, const int* ts, int nt, double* mom) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
+    if (nt == 0) return;
+    if (!mom) throw hbm::Error(1, "bad output");
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.mom = mom;
+    observe_slots(h, slots, 0, o, nullptr, nullptr);
+  });
+}
+
+int hbm_observe_moments_states(hbm_engine* h, int n, const int* dims, const double* const* data, double* mom) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data || !mom))) throw hbm::Error(1, "bad argument");
+    if (n == 0) return;
+    staged_check(E, n, dims, -1);
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.mom = mom;
+    observe_staged(h, n, dims, data, o, nullptr, nullptr);
   });
 }
 

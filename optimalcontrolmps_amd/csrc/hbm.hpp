@@ -79,6 +79,9 @@ int hbm_fock_amplitudes_states(hbm_engine* h, int n, const int* dims, const doub
                                const signed char* configs, int nconf, double* amp);
 int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const double* const* data, int wcap,
                                 double* entropy, double* schmidt, int* sector);
+// ocg_observe_moments / ocg_observe_moments_states (observe_energy.hpp)
+int hbm_observe_moments(hbm_engine* h, int which, const int* ts, int nt, double* mom);
+int hbm_observe_moments_states(hbm_engine* h, int n, const int* dims, const double* const* data, double* mom);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM
 // kernel (k_gemm) with its algorithmic bytes and flops; 9: the observable kernels
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps);

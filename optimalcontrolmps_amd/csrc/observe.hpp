@@ -13,6 +13,9 @@
 // A·Renv^H, the new environments sum_n A^H·(E·A), and the closes
 // sum conj(X)∘Y.  Every dependency is a kernel boundary on one stream.
 //
+// With Want::mom the chunk runs observe_energy.hpp's moment sweep instead
+// (ocg_observe_moments).
+//
 // With a Spec the spectrum stages follow the sweeps (ocg_observe_spectrum):
 // the Schmidt weights and entropies of every bond from Lenv_b and Renv_b on
 // observe_eig.hpp's batched Jacobi eigensolver (see run_chunk).
@@ -75,6 +78,7 @@ struct CTask {
 struct Want {
   bool norm = false, occ = false, ada = false, nn = false;
   bool spec = false;  // Schmidt weights and entropies of every bond (run_chunk's Spec argument)
+  bool mom = false;   // the energy moments alone (observe_energy.hpp)
   bool env() const { return occ || ada || nn; }
 };
 // the spectrum results of one chunk (device addresses, valid until the chunk's sync)
@@ -109,7 +113,7 @@ struct Snap {
   signed char* d_config = nullptr;          // device [state][nper][L] (draw mode)
   double* d_val = nullptr;                  // device: logp [state][nper], or amplitudes [state][nper][2]
 };
-// where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn
+// where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn, 4 a real moment, 5 <K D> (complex)
 struct Dest {
   int kind;
   size_t idx;
@@ -118,6 +122,12 @@ struct Traffic {
   double bytes = 0, flops = 0;
   long launches = 0;
 };
+
+}  // namespace obs
+
+#include "observe_energy.hpp"
+
+namespace obs {
 
 // ------------------------------------------------------------------ kernels
 namespace {
@@ -225,6 +235,7 @@ __global__ __launch_bounds__(kCloseNT) void k_obs_close(const CTask* __restrict_
 //   int eig(std::vector<ETask>&, int* status)     one eigen stage; returns its launches
 //   void entropy(std::vector<STask>&, double* out)
 //   void sample(SampleTable&, const SArgs&)          the snapshot launch of the chunk
+//   void energy(EnergyTable&, const EArgs&, std::vector<double>& coef)   the moment chain launch
 
 // dry run: the workspace a chunk would take (256-byte granules, as the arenas)
 struct CountBackend {
@@ -262,6 +273,9 @@ struct CountBackend {
   void sample(SampleTable& tb, const SArgs&) {
     bytes += al(sizeof(SBlk) * tb.blk.size()) + al(sizeof(double*) * tb.renv.size()) +
              al(sizeof(SState) * tb.st.size()) + al(tb.given.size());
+  }
+  void energy(EnergyTable& tb, const EArgs&, std::vector<double>& coef) {
+    bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()) + al(sizeof(double) * coef.size());
   }
 };
 
@@ -367,12 +381,16 @@ struct RawBackend {
   void sample(SampleTable& tb, const SArgs& a) {
     if (ok()) note(sample_launch(tb, a, st, [&](auto& v) { return upload(v); }));
   }
+  void energy(EnergyTable& tb, const EArgs& a, std::vector<double>& coef) {
+    std::vector<double> cf = coef;  // (upload takes its vector)
+    if (ok()) note(energy_launch(tb, a, cf, st, [&](auto& v) { return upload(v); }));
+  }
 };
 
 // ------------------------------------------------------------------ driver
 // close outputs one state can produce (sizes its slice of the result buffer)
 inline size_t max_outputs(int L, int p, int nrows, Want w) {
-  return 1 + (w.env() ? size_t(L) * p : 0) + 2 * size_t(nrows) * L;
+  return 1 + (w.env() ? size_t(L) * p : 0) + 2 * size_t(nrows) * L + (w.mom ? size_t(kEnergyOut) : 0);
 }
 
 // Queue every launch of one chunk.  out_slot[i] is state i's index in the
@@ -394,6 +412,10 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
   dests.clear();
   double* d_out = be.alloc(size_t(B) * max_outputs(L, p, R, want));
   const double* one = be.one();
+  if (want.mom) {
+    energy_chunk(be, L, p, Q, S, out_slot, d_out, one, dests, tr);
+    return d_out;
+  }
   auto D = [&](int i, int b, int q) { return (q < 0 || q > Q) ? 0 : S[i]->dims[size_t(b) * Q1 + q]; };
   auto A = [&](int i, int k, int q, int n) -> Blk {
     if (q < 0 || n < 0 || n >= p || q + n > Q) return Blk{};
@@ -839,6 +861,7 @@ struct Outputs {
   double* nn = nullptr;
   int L = 0, p = 0, nrows = 0;
   const int* rows = nullptr;
+  double* mom = nullptr;  // [nt][7]: alone (ocg_observe_moments)
 };
 
 // what the kernels must compute for the requested outputs (the diagonal of a
@@ -849,6 +872,7 @@ inline Want want_of(const Outputs& o) {
   w.ada = o.ada != nullptr && o.nrows > 0;
   w.nn = o.nn != nullptr && o.nrows > 0;
   w.occ = o.occ != nullptr || w.ada || w.nn;
+  w.mom = o.mom != nullptr;
   return w;
 }
 
@@ -865,6 +889,11 @@ inline void scatter(const std::vector<Dest>& dests, const double* res, const Out
         o.ada[2 * d.idx + 1] = res[2 * j + 1];
         break;
       case 3: o.nn[d.idx] = res[2 * j]; break;
+      case 4: o.mom[d.idx] = res[2 * j]; break;
+      case 5:
+        o.mom[d.idx] = res[2 * j];
+        o.mom[d.idx + 1] = res[2 * j + 1];
+        break;
     }
   }
 }

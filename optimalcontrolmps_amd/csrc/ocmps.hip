@@ -1853,11 +1853,16 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
   const int nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !sn) return 0;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !sn) return 0;
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
     if (wo > obs::kSampleMaxOrder) return fail(c, OCG_ECAP, "snapshots: a bond sector above order 512");
+  }
+  if (want.mom) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
+    if (wo > obs::kEnergyMaxOrder) return fail(c, OCG_ECAP, "moments: a bond sector above order 512");
   }
   if (so) {
     int wb = 0, wo = 0;
@@ -1874,9 +1879,9 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if (sn && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      return fail(c, OCG_ENOMEM, "snapshots: the workspace of one state (" + std::to_string(sum) +
-                                     " B) exceeds the chunk budget");
+    if ((sn || want.mom) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : "moments") + ": the workspace of one state (" +
+                                     std::to_string(sum) + " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
@@ -2222,6 +2227,31 @@ int ocg_fock_amplitudes_states(ocg_ctx* c, int n, const int* dims, const double*
   sn.given = configs;
   sn.val = amp;
   return observe_staged(c, n, dims, data, o, nullptr, &sn, "amplitudes");
+}
+
+int ocg_observe_moments(ocg_ctx* c, int which, const int* ts, int nt, double* mom) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_moments(c->hbm, which, ts, nt, mom));
+  std::vector<int> slots;
+  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
+  if (nt == 0) return 0;
+  if (!mom) return fail(c, OCG_EINVAL, "bad output");
+  HIPCHK(c, hipSetDevice(c->device));
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.mom = mom;
+  return observe_slots(c, slots, 0, o, nullptr, nullptr);
+}
+
+int ocg_observe_moments_states(ocg_ctx* c, int n, const int* dims, const double* const* data, double* mom) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_moments_states(c->hbm, n, dims, data, mom));
+  if (n < 0 || (n > 0 && (!dims || !data || !mom))) return fail(c, OCG_EINVAL, "bad argument");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = staged_check(c, n, dims, -1)) return rc;
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.mom = mom;
+  return observe_staged(c, n, dims, data, o, nullptr, nullptr, "moments");
 }
 
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,

@@ -359,6 +359,20 @@ class GpuTDMRG::Engine {
                   c, "ocg_fock_amplitudes");
     return amp;
   }
+  // Energy moments of the device-resident trajectory (ocg_observe_moments): norm2,
+  // <K>, <D>, <K K>, <D D>, <K D> of the states ts (empty: all N), from which
+  // TrajectoryMoments gives <H(J, U)> and its variance for any (J, U).
+  TrajectoryMoments observeMoments(int which = 0, const std::vector<int>& ts = {}) {
+    TrajectoryMoments o;
+    o.ts = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) o.ts.push_back(int(t));
+    o.mom.assign(7 * o.ts.size(), 0.0);
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_observe_moments(c, which, o.ts.data(), int(o.ts.size()), o.mom.data()), c,
+                  "ocg_observe_moments");
+    return o;
+  }
   std::vector<MPS> psiTrajectory() {
     std::vector<MPS> out;
     for (size_t t = 0; t < N; ++t)

@@ -13,6 +13,9 @@
 //                   tau^2 Trotter fixed-point infidelity: 6e-8 at L=5, U=2.5)
 //   defaults        maxBondDim 200, threshold 1e-9 (the overload without
 //                   them, :18-60: sweeps.maxm() up to 200, cutoff 1e-9)
+//   certificate     optional out-parameters: the energy <H(J, U)> of the returned
+//                   state, its variance <H^2> - <H>^2 (0 for an eigenstate) and the
+//                   seven raw moments behind them (ocg_observe_moments_states)
 #pragma once
 
 #include <cmath>
@@ -50,7 +53,8 @@ inline void check(int rc, const ocg_ctx* c, const char* what) {
 }  // namespace detail_gs
 
 inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const double J, const double U,
-                           const int maxBondDim, const double threshold, bool /*silent*/ = true, int device = 0) {
+                           const int maxBondDim, const double threshold, bool /*silent*/ = true, int device = 0,
+                           double* energy = nullptr, double* variance = nullptr, double* moments7 = nullptr) {
   const int L = sites.N(), p = sites.localDim();
   MPS psi = productState(L, p, Npart);
   ocg_ctx* c = nullptr;
@@ -75,6 +79,16 @@ inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const doub
         psi = std::move(nw);
         if (1.0 - std::hypot(ov[0], ov[1]) < 1e-13) break;
       }
+    }
+    if (energy || variance || moments7) {
+      double m[7];
+      const double* data[1] = {psi.raw()};
+      detail_gs::check(ocg_observe_moments_states(c, 1, psi.dims.data(), data, m), c, "ocg_observe_moments_states");
+      const double e = (-J * m[1] + U * m[2]) / m[0];
+      if (energy) *energy = e;
+      if (variance) *variance = (J * J * m[3] - 2 * J * U * m[5] + U * U * m[4]) / m[0] - e * e;
+      if (moments7)
+        for (int j = 0; j < 7; ++j) moments7[j] = m[j];
     }
   } catch (...) {
     ocg_destroy(c);

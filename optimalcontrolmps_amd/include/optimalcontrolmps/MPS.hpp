@@ -72,6 +72,32 @@ struct MPS {
   const double* raw() const { return reinterpret_cast<const double*>(data.data()); }
 };
 
+// Energy moments of stored states (ocg_observe_moments): for H(J, U) = -J K + U D with
+// K the hopping sum and D = sum_i n_i (n_i - 1) / 2, per entry e the raw numbers
+// norm2, <K>, <D>, <K K>, <D D>, Re <K D>, Im <K D> (none divided by norm2).
+struct TrajectoryMoments {
+  std::vector<int> ts;      // [e] state index
+  std::vector<double> mom;  // [e][7]
+  size_t size() const { return ts.size(); }
+  const double* at(size_t e) const { return mom.data() + 7 * e; }
+  double norm2(size_t e) const { return at(e)[0]; }
+  double k1(size_t e) const { return at(e)[1]; }
+  double d1(size_t e) const { return at(e)[2]; }
+  // <H(J, U)> = (-J k1 + U d1) / norm2
+  double energy(size_t e, double J, double U) const { return (-J * at(e)[1] + U * at(e)[2]) / at(e)[0]; }
+  // <H^2> - <H>^2
+  double energyVariance(size_t e, double J, double U) const {
+    const double* m = at(e);
+    const double en = energy(e, J, U);
+    return (J * J * m[3] - 2 * J * U * m[5] + U * U * m[4]) / m[0] - en * en;
+  }
+};
+// E_t = <H(u_t)> and Var_t of the stored psi_t (OptimalControl::getPsitEnergies)
+struct TrajectoryEnergies {
+  TrajectoryMoments moments;
+  std::vector<double> energy, variance;  // [e]
+};
+
 // Observables of nt trajectory states evaluated on the device (ocg_observe,
 // ocg_observe_spectrum, include/ocmps.h): what GpuTDMRG::Engine::observe and
 // OptimalControl::getPsitObservables return and the overloads of

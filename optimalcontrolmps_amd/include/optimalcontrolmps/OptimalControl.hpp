@@ -16,6 +16,7 @@
 //           needs the first, and the second when entropies are asked for),
 //           sample(which, ts, nshots, seed), fockAmplitudes(which, ts, configs) (optional: samplePsit,
 //           getPsitFockProbability),
+//           observeMoments(which, ts) (optional: getPsitEnergies, with the stepper's hopping()),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -88,6 +89,24 @@ class OptimalControl {
     stdvec pr(amp.size());
     for (size_t e = 0; e < amp.size(); ++e) pr[e] = o.norm2[e] > 0 ? std::norm(amp[e]) / o.norm2[e] : 0.0;
     return pr;
+  }
+  // E_t = <psi_t|H(u_t)|psi_t> / <psi_t|psi_t> and Var_t = <H(u_t)^2> - E_t^2 of the stored
+  // psi_t with u = the control as given to the last propagation (GROUP coefficients are
+  // converted) and the stepper's J: the drift of E over stretches of constant u measures
+  // Trotter plus truncation error, E_T - E_0(u_T) is the residual energy of a ramp.  Reads the
+  // device trajectory (Engine::observeMoments); nothing is propagated.  Only for steppers
+  // whose Engine has observeMoments() and that have hopping() (GpuTDMRG).
+  ocmps::TrajectoryEnergies getPsitEnergies(const stdvec& control) {
+    const stdvec u = GRAPE ? control : basis.convertControl(control);
+    if (u.size() != N) throw std::invalid_argument("getPsitEnergies: control has the wrong length");
+    ocmps::TrajectoryEnergies r;
+    r.moments = engine->observeMoments(0, {});
+    const double J = timeStepper.hopping();
+    for (size_t t = 0; t < r.moments.size(); ++t) {
+      r.energy.push_back(r.moments.energy(t, J, u[t]));
+      r.variance.push_back(r.moments.energyVariance(t, J, u[t]));
+    }
+    return r;
   }
   size_t getM() const { return M; }
   size_t getN() const { return N; }

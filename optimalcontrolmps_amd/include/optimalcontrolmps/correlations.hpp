@@ -378,6 +378,12 @@ inline double correlationTerm(const BoseHubbard& sites, const MPS& psi, const st
   return *std::max_element(w.begin(), w.end());
 }
 
+// <H(J, U)> and <H^2> - <H>^2 of entry e of device moments (Engine::observeMoments)
+inline double energy(const TrajectoryMoments& m, size_t e, double J, double U) { return m.energy(e, J, U); }
+inline double energyVariance(const TrajectoryMoments& m, size_t e, double J, double U) {
+  return m.energyVariance(e, J, U);
+}
+
 // the entropies the device computed for entry e (bonds b = 1..N-1); throws
 // std::invalid_argument when they were not requested
 inline std::vector<double> entanglementEntropy(const TrajectoryObservables& o, size_t e) {

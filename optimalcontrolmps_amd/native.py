@@ -45,9 +45,9 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
                   "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
-                  "observe_eig.hpp", "observe_sample.hpp"],
+                  "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp"],
         "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
-                "observe_eig.hpp", "observe_sample.hpp"],
+                "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -136,6 +136,8 @@ SIGNATURES = [
     ("ocg_sample_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), C.c_int, C.c_ulonglong, bp, dp]),
     ("ocg_fock_amplitudes", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, bp, C.c_int, dp]),
     ("ocg_fock_amplitudes_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), bp, C.c_int, dp]),
+    ("ocg_observe_moments", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, dp]),
+    ("ocg_observe_moments_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), dp]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -188,6 +190,20 @@ class MPS:
 
     def copy(self):
         return MPS(self.L, self.p, self.Q, self.dims.copy(), self.data.copy())
+
+
+def energy(mom, J, U):
+    """<H(J, U)> = (-J k1 + U d1) / norm2 from moments (..., 7) of Engine.moments()"""
+    mom = np.asarray(mom, np.float64)
+    return (-J * mom[..., 1] + U * mom[..., 2]) / mom[..., 0]
+
+
+def energy_variance(mom, J, U):
+    """<H^2> - <H>^2 = (J^2 kk - 2 J U kd_re + U^2 dd) / norm2 - E^2 from moments (..., 7); U may be an
+    array over the leading axes (the control of each stored state)"""
+    mom = np.asarray(mom, np.float64)
+    return (J * J * mom[..., 3] - 2 * J * U * mom[..., 5] + U * U * mom[..., 4]) / mom[..., 0] \
+        - energy(mom, J, U) ** 2
 
 
 class Engine:
@@ -606,6 +622,30 @@ class Engine:
         dims, raws, data = self._staged(states)
         self._chk(lib().ocg_fock_amplitudes_states(self.h, n, dims.ctypes.data_as(ip), data, cf.ctypes.data_as(bp),
                                                    len(cf), out.ctypes.data_as(dp)), "ocg_fock_amplitudes_states")
+        return out
+
+    def moments(self, which=0, ts=None):
+        """Energy moments of the device trajectory states (ocg_observe_moments): which /
+        ts as observe().  Returns (nt, 7): norm2, k1 = <K>, d1 = <D>, kk = <K K>,
+        dd = <D D>, kd_re, kd_im = <K D>, raw (not divided by norm2), for H = -J K + U D
+        with K the hopping sum and D = sum n (n - 1) / 2: see energy() and
+        energy_variance() of this module."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        out = np.zeros((len(tt), 7))
+        self._chk(lib().ocg_observe_moments(self.h, int(which), pt, len(tt), out.ctypes.data_as(dp)),
+                  "ocg_observe_moments")
+        return out
+
+    def moments_states(self, states):
+        """moments() for caller-supplied host states of any gauge or norm
+        (ocg_observe_moments_states)."""
+        n = len(states)
+        out = np.zeros((n, 7))
+        if n == 0:
+            return out
+        dims, raws, data = self._staged(states)
+        self._chk(lib().ocg_observe_moments_states(self.h, n, dims.ctypes.data_as(ip), data, out.ctypes.data_as(dp)),
+                  "ocg_observe_moments_states")
         return out
 
     def stats(self, kind):

@@ -2,7 +2,7 @@
 was before: one ocg_get_state copy per state (a lower bound of that path, which
 adds the host contraction of correlations.hpp on top).
 
-    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|all] [--reps R] [--out DIR]
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|e1|e4|all] [--reps R] [--out DIR]
 
 One process; every shape is warmed up; each timed call ends in a device
 synchronise (both entry points return only after their results are on the
@@ -25,6 +25,13 @@ with the copy loop; the path they replace is that loop plus N_t times the host
 sampleFock(psi, 1024, seed, t) of one mid-trajectory state, timed on one thread by
 a small stand-alone program.  Writes observe_sample_config1.json /
 observe_sample_config4.json.
+
+e1 / e4: the energy moments (ocg_observe_moments) of every state at the same two
+shapes, alternating with the copy loop alone, which is the lower bound of the
+only other route to <H^2> (copy every state out and contract on the host); at
+config 1 the chain kernel also alternates with the forced task-list path
+(OCG_OBS_ENERGY_CHAIN=0).  Writes observe_energy_config1.json /
+observe_energy_config4.json.
 """
 from __future__ import annotations
 
@@ -272,20 +279,101 @@ def sample4(reps):
     return res
 
 
+def energy_cases(eng, Nt, reps, warm, both_paths):
+    """the moments of every state (on the chain kernel where the widths allow, and with the task lists
+    forced), and the copy loop, alternating; kind 9 per moments case from a pass of its own"""
+    dims = np.zeros((eng.L + 1) * (eng.Q + 1), np.int32)
+    data = np.zeros(2 * eng.cap)
+
+    def forced_lists():
+        os.environ["OCG_OBS_ENERGY_CHAIN"] = "0"
+        try:
+            return eng.moments(0)
+        finally:
+            del os.environ["OCG_OBS_ENERGY_CHAIN"]
+    cases = {"moments": lambda: eng.moments(0)}
+    if both_paths:
+        cases["moments_lists"] = forced_lists
+    cases["get_state_copies"] = lambda: copy_all(eng, 0, Nt, dims, data)
+    for f in cases.values():
+        for _ in range(warm):
+            f()
+    t = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    res = {k: spread(v) for k, v in t.items()}
+    for k in cases:
+        if k.startswith("moments"):
+            eng.reset_stats()
+            cases[k]()
+            res[k + "_kind9"] = eng.stats(9)
+            res[k + "_kind7_ms"] = eng.stats(7)["ms"]
+            res[k + "_vs_copies"] = res["get_state_copies"]["median_ms"] / res[k]["median_ms"]
+    if both_paths:
+        res["chain_vs_lists"] = res["moments_lists"]["median_ms"] / res["moments"]["median_ms"]
+        a, b = eng.moments(0), forced_lists()
+        res["chain_lists_max_rel_dev"] = float(np.abs(a - b).max() / np.abs(b).max())
+    return res
+
+
+def energy1(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    u = np.linspace(2.5, 50.0, Nt)
+    eng.propagate(u, 1)
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine (no k_gemm: kind 7 is 0), all t",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1)))}
+    res.update(energy_cases(eng, Nt, reps, 2, True))
+    mom = eng.moments(0)
+    res["energy_first_last"] = [float(native.energy(mom[0], J, u[0])), float(native.energy(mom[-1], J, u[-1]))]
+    res["variance_first_last"] = [float(native.energy_variance(mom[0], J, u[0])),
+                                  float(native.energy_variance(mom[-1], J, u[-1]))]
+    return res
+
+
+def energy4(reps):
+    L, p, Q, J, dt, cut, maxm, Nt = 20, 7, 20, 1.0, 0.005, 1e-8, 256, 33
+    z = np.load(os.path.join(GOLDEN, "c4_warm256.npz"), allow_pickle=False)
+    c4 = np.load(os.path.join(GOLDEN, "c4.npz"), allow_pickle=False)
+    u = np.load(os.path.join(GOLDEN, "c4_w256h33.npz"), allow_pickle=False)["u"]
+    eng = Engine(L, p, Q, J, dt, cut, maxm, engine="hbm")
+    eng.set_states(MPS(L, p, Q, c4["w256h/tgt_dims"], c4["w256h/tgt_data"]), MPS(L, p, Q, z["dims"], z["data"]))
+    eng.propagate(u, 1)
+    res = {"config": "4 slice: L=20 p=7 Q=20 chi=256 (warm state) N_t=33, HBM engine (task-list path)",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1)))}
+    res.update(energy_cases(eng, Nt, reps, 1, False))
+    k9 = res["moments_kind9"]
+    res["per_state_ms"] = res["moments"]["median_ms"] / Nt
+    res["kind9_tflops"] = 1e-9 * k9["alg_flops"] / k9["ms"] if k9["ms"] else None
+    res["k_gemm_share_of_kind9_time"] = res["moments_kind7_ms"] / k9["ms"] if k9["ms"] else None
+    mom = eng.moments(0)
+    res["energy_first_last"] = [float(native.energy(mom[0], J, u[0])), float(native.energy(mom[-1], J, u[-1]))]
+    res["variance_first_last"] = [float(native.energy_variance(mom[0], J, u[0])),
+                                  float(native.energy_variance(mom[-1], J, u[-1]))]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "all"])
+    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "e1", "e4", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4)),
                            ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4)),
-                           ("p1", sample1, a.reps), ("p4", sample4, max(3, a.reps // 4))):
+                           ("p1", sample1, a.reps), ("p4", sample4, max(3, a.reps // 4)),
+                           ("e1", energy1, a.reps), ("e4", energy4, max(3, a.reps // 4))):
         if a.config in (name, "all"):
             res = fn(reps)
             res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
-            kind = {"s": "observe_spectrum_config", "p": "observe_sample_config"}.get(name[0], "observe_config")
+            kind = {"s": "observe_spectrum_config", "p": "observe_sample_config",
+                    "e": "observe_energy_config"}.get(name[0], "observe_config")
             out = f"{kind}{name[-1]}.json"
             with open(os.path.join(a.out, out), "w") as f:
                 json.dump(res, f, indent=1)
