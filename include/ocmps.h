@@ -84,7 +84,8 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * 4 ocg_observe, ocg_observe_states, ocg_kernel_stats kind 9;
  * 5 ocg_observe_spectrum, ocg_observe_spectrum_states;
  * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states;
- * 7 ocg_observe_moments, ocg_observe_moments_states. */
+ * 7 ocg_observe_moments, ocg_observe_moments_states; added within 7 (no existing
+ * entry point or struct changed): ocg_observe_pairs, ocg_observe_pairs_states. */
 #define OCG_ABI_VERSION 7
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
@@ -345,6 +346,36 @@ int ocg_observe_moments(ocg_ctx* ctx, int which, const int* ts, int nt, double* 
  * gauge or norm, zero-padded sectors allowed), staged on the device in batches. */
 int ocg_observe_moments_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, double* mom);
 
+/* Transition matrix elements between two stored states.  Pair e has the bra x (state
+ * tx[e] of trajectory which_x) and the ket y (state ty[e] of which_y); which 0 psi_t,
+ * 1 xi_t, 2 xiH_t, existence rules, OCG_ESTATE / OCG_EINVAL as ocg_observe; tx == NULL
+ * or ty == NULL means 0..npairs-1; npairs == 0 writes nothing.  The outputs are
+ * complex, interleaved (re, im) and raw (nothing is divided by a norm); a NULL output
+ * is skipped and its work is not done:
+ *   ovl[npairs][2]            <x|y>
+ *   occ[npairs][L][p][2]      <x|P_k(n)|y>, P_k(n) the projector on occupation n of site
+ *                             k: <x|n_k|y> = sum_n n occ, <x|D|y> = sum_k sum_n n (n - 1) / 2 occ
+ *   hop[npairs][L-1][2][2]    [b-1][0] = <x|a+_b a_{b+1}|y>, [b-1][1] = <x|a_b a+_{b+1}|y>
+ *                             (a, a+ cut at p levels, as the gates); <x|K|y> = the sum of
+ *                             both over b.
+ * Gauge free, environments from both ends as ocg_observe; they are rectangular (block
+ * q is d_x[b][q] x d_y[b][q]), so x and y may have different bond dimensions, and a
+ * sector only one of them has contributes nothing.  Any norm.  Chunking and
+ * OCG_OBS_BUDGET as ocg_observe_moments (OCG_ENOMEM if one pair's workspace exceeds the
+ * chunk budget); bond sectors of order up to 512 (OCG_ECAP above).  Pairs whose sectors
+ * are all at most 16 wide, both states, run in one kernel per chunk (OCG_OBS_PAIR_CHAIN=0:
+ * the task-list path for all, 5 L - 2 launches per chunk, 2 L + 1 for ovl alone; the two
+ * agree to rounding, not bit for bit).  A pair's numbers depend on the pair and its
+ * path alone: bit-identical whatever else is requested, in whatever order, and however
+ * the request is chunked.  Reads the trajectories only.  Counted in ocg_kernel_stats
+ * kind 9. */
+int ocg_observe_pairs(ocg_ctx* ctx, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
+                      double* occ, double* hop);
+/* The same for n pairs of caller-supplied host states (x[e], y[e]; any gauge or norm,
+ * zero-padded sectors allowed), staged on the device in batches. */
+int ocg_observe_pairs_states(ocg_ctx* ctx, int n, const int* dims_x, const double* const* x, const int* dims_y,
+                             const double* const* y, double* ovl, double* occ, double* hop);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -380,7 +411,7 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
  * segment length of the last one), 9 the observable kernels of ocg_observe /
  * ocg_observe_states / ocg_observe_spectrum[_states] / ocg_sample[_states] /
- * ocg_fock_amplitudes[_states] / ocg_observe_moments[_states] (HIP-event time of their chunks, kernel launches, and the
+ * ocg_fock_amplitudes[_states] / ocg_observe_moments[_states] / ocg_observe_pairs[_states] (HIP-event time of their chunks, kernel launches, and the
  * algorithmic bytes and flops of the host-built task lists).  Sums since the
  * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,

@@ -3209,6 +3209,9 @@ struct ObsBackend {
   void energy(obs::EnergyTable& tb, const obs::EArgs& a, std::vector<double>& coef) {
     HCK(obs::energy_launch(tb, a, coef, E.st, [&](auto& v) { return E.upload(v); }));
   }
+  void pair(obs::PairTable& tb, const obs::PArgs& a) {
+    HCK(obs::pair_launch(tb, a, E.st, [&](auto& v) { return E.upload(v); }));
+  }
 };
 
 obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
@@ -3232,7 +3235,8 @@ obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
 // the observables of state slots[i] into entry out0 + i of the outputs, in
 // chunks whose workspace fits half the free HBM
 void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr);
+                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr,
+                   const std::vector<obs::StateDesc>* kets = nullptr);
 // with so the spectrum stages run too and their results go to *so; with sn the snapshot
 // launch follows the right sweep instead and its results go to sn's outputs
 void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
@@ -3248,18 +3252,28 @@ void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, co
   observe_descs(h, desc, out0, o, occ_buf, so, sn);
 }
 
-// the chunks of observe.hpp's driver over states described on the device
+// the chunks of observe.hpp's driver over states described on the device (with kets: over the pairs
+// bra desc[i], ket (*kets)[i])
 void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn) {
+                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn,
+                   const std::vector<obs::StateDesc>* kets) {
   hbm::Engine& E = *h->E;
   const int L = E.L, nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !sn) return;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !sn) return;
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
     if (wo > obs::kSampleMaxOrder) throw hbm::Error(2, "snapshots: a bond sector above order 512");
+  }
+  if (want.pair) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) {
+      obs::widest(desc[i], L, E.Q1, wb, wo);
+      obs::widest((*kets)[i], L, E.Q1, wb, wo);
+    }
+    if (wo > obs::kPairMaxOrder) throw hbm::Error(2, "pairs: a bond sector above order 512");
   }
   if (want.mom) {
     int wb = 0, wo = 0;
@@ -3275,19 +3289,21 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     if (wo > obs::kEigMaxOrder) throw hbm::Error(2, "spectrum: a bond sector above order 512");
   }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want, sn);
+  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want, sn, kets);
   const size_t budget = obs::chunk_budget();
   for (int i0 = 0; i0 < nst;) {
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      throw hbm::Error(6, std::string(sn ? "snapshots" : "moments") + ": the workspace of one state (" +
+    if ((sn || want.mom || want.pair) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      throw hbm::Error(6, std::string(sn ? "snapshots" : want.pair ? "pairs" : "moments") +
+                              ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
                               std::to_string(sum) + " B) exceeds the chunk budget");
-    std::vector<const obs::StateDesc*> S;
+    std::vector<const obs::StateDesc*> S, SY;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
       S.push_back(&desc[i]);
+      if (kets) SY.push_back(&(*kets)[i]);
       os.push_back(out0 + i);
     }
     ObsBackend be{E};
@@ -3295,7 +3311,8 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     Timer t(h, 9);
     obs::Spec sp;
     const double* d_out =
-        obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr, sn);
+        obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr, sn,
+                       kets ? &SY : nullptr);
     if (sn) HCK(sn->fetch(out0 + i0, S.size(), L, E.st));
     std::vector<double> res(2 * std::max<size_t>(dests.size(), 1));
     if (!dests.empty())
@@ -3364,28 +3381,38 @@ void staged_check(const hbm::Engine& E, int n, const int* dims, int wcap) {
 // itself: its blocks are the contiguous row-major matrices the descriptors want, and a
 // sector may be larger than the Hilbert-space bound of the state slots (a padded or
 // over-parametrised state).
+// With dims_y / data_y the states are the bras of pairs and those the kets, staged behind them.
 void observe_staged(hbm_engine* h, int n, const int* dims, const double* const* data, const obs::Outputs& o,
-                    const obs::SpecOutputs* so, obs::Snap* sn) {
+                    const obs::SpecOutputs* so, obs::Snap* sn, const int* dims_y = nullptr,
+                    const double* const* data_y = nullptr) {
   hbm::Engine& E = *h->E;
   const int nsq = (E.L + 1) * E.Q1;
   const int B = std::min(n, 64);
   for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb = std::min(B, n - i0);
+    const int nb0 = std::min(B, n - i0), nb = dims_y ? 2 * nb0 : nb0;
+    // entry i of the batch: state i0 + i, or for i >= nb0 the ket i0 + i - nb0
+    auto dims_of = [&](int i) { return i < nb0 ? dims + size_t(i0 + i) * nsq : dims_y + size_t(i0 + i - nb0) * nsq; };
+    auto data_of = [&](int i) { return i < nb0 ? data[i0 + i] : data_y[i0 + i - nb0]; };
     std::vector<size_t> at(nb + 1, 0);
     for (int i = 0; i < nb; ++i) {
       obs::StateDesc tmp;
-      at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, nullptr, tmp);
+      at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims_of(i), nullptr, tmp);
     }
     hbm::DBuf<double> stage;
     stage.reserve(2 * std::max<size_t>(at[nb], 1));
     std::vector<obs::StateDesc> desc(nb);
     for (int i = 0; i < nb; ++i) {
       if (at[i + 1] > at[i])
-        HCK(hipMemcpyAsync(stage.p + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
+        HCK(hipMemcpyAsync(stage.p + 2 * at[i], data_of(i), 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
                            E.st));
-      obs::compact_desc(E.L, E.p, E.Q, dims + size_t(i0 + i) * nsq, stage.p + 2 * at[i], desc[i]);
+      obs::compact_desc(E.L, E.p, E.Q, dims_of(i), stage.p + 2 * at[i], desc[i]);
     }
-    observe_descs(h, desc, size_t(i0), o, nullptr, so, sn);
+    std::vector<obs::StateDesc> kets;
+    if (dims_y) {
+      kets.assign(desc.begin() + nb0, desc.end());
+      desc.resize(nb0);
+    }
+    observe_descs(h, desc, size_t(i0), o, nullptr, so, sn, dims_y ? &kets : nullptr);
     E.sync();
   }
 }
@@ -3624,6 +3651,42 @@ int hbm_observe_moments_states(hbm_engine* h, int n, const int* dims, const doub
     obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
     o.mom = mom;
     observe_staged(h, n, dims, data, o, nullptr, nullptr);
+  });
+}
+
+int hbm_observe_pairs(hbm_engine* h, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
+                      double* occ, double* hop) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    const std::vector<int> sx = trajectory_slots(h, which_x, tx, npairs, nullptr);
+    const std::vector<int> sy = trajectory_slots(h, which_y, ty, npairs, nullptr);
+    if (npairs == 0 || (!ovl && !occ && !hop)) return;
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.povl = ovl;
+    o.pocc = occ;
+    o.phop = hop;
+    std::vector<obs::StateDesc> dx(npairs), dy(npairs);
+    for (int i = 0; i < npairs; ++i) {
+      dx[i] = obs_desc(E, E.states[sx[i]]);
+      dy[i] = obs_desc(E, E.states[sy[i]]);
+    }
+    observe_descs(h, dx, 0, o, nullptr, nullptr, nullptr, &dy);
+  });
+}
+
+int hbm_observe_pairs_states(hbm_engine* h, int n, const int* dims_x, const double* const* x, const int* dims_y,
+                             const double* const* y, double* ovl, double* occ, double* hop) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims_x || !x || !dims_y || !y))) throw hbm::Error(1, "bad argument");
+    if (n == 0 || (!ovl && !occ && !hop)) return;
+    staged_check(E, n, dims_x, -1);
+    staged_check(E, n, dims_y, -1);
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.povl = ovl;
+    o.pocc = occ;
+    o.phop = hop;
+    observe_staged(h, n, dims_x, x, o, nullptr, nullptr, dims_y, y);
   });
 }
 

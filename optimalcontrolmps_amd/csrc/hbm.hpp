@@ -82,6 +82,11 @@ int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const dou
 // ocg_observe_moments / ocg_observe_moments_states (observe_energy.hpp)
 int hbm_observe_moments(hbm_engine* h, int which, const int* ts, int nt, double* mom);
 int hbm_observe_moments_states(hbm_engine* h, int n, const int* dims, const double* const* data, double* mom);
+// ocg_observe_pairs / ocg_observe_pairs_states (observe_pair.hpp)
+int hbm_observe_pairs(hbm_engine* h, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
+                      double* occ, double* hop);
+int hbm_observe_pairs_states(hbm_engine* h, int n, const int* dims_x, const double* const* x, const int* dims_y,
+                             const double* const* y, double* ovl, double* occ, double* hop);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM
 // kernel (k_gemm) with its algorithmic bytes and flops; 9: the observable kernels
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps);

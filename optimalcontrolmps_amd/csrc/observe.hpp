@@ -16,6 +16,9 @@
 // With Want::mom the chunk runs observe_energy.hpp's moment sweep instead
 // (ocg_observe_moments).
 //
+// With Want::pair the chunk is a list of (bra, ket) pairs and runs observe_pair.hpp's
+// transition sweeps (ocg_observe_pairs).
+//
 // With a Spec the spectrum stages follow the sweeps (ocg_observe_spectrum):
 // the Schmidt weights and entropies of every bond from Lenv_b and Renv_b on
 // observe_eig.hpp's batched Jacobi eigensolver (see run_chunk).
@@ -33,6 +36,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -79,6 +83,7 @@ struct Want {
   bool norm = false, occ = false, ada = false, nn = false;
   bool spec = false;  // Schmidt weights and entropies of every bond (run_chunk's Spec argument)
   bool mom = false;   // the energy moments alone (observe_energy.hpp)
+  bool pair = false, pair_occ = false, pair_hop = false;  // transition elements of pairs alone (observe_pair.hpp)
   bool env() const { return occ || ada || nn; }
 };
 // the spectrum results of one chunk (device addresses, valid until the chunk's sync)
@@ -113,7 +118,8 @@ struct Snap {
   signed char* d_config = nullptr;          // device [state][nper][L] (draw mode)
   double* d_val = nullptr;                  // device: logp [state][nper], or amplitudes [state][nper][2]
 };
-// where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn, 4 a real moment, 5 <K D> (complex)
+// where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn, 4 a real moment, 5 <K D> (complex),
+// 6 / 7 / 8 a pair's ovl / occ / hop (complex)
 struct Dest {
   int kind;
   size_t idx;
@@ -126,6 +132,7 @@ struct Traffic {
 }  // namespace obs
 
 #include "observe_energy.hpp"
+#include "observe_pair.hpp"
 
 namespace obs {
 
@@ -236,6 +243,7 @@ __global__ __launch_bounds__(kCloseNT) void k_obs_close(const CTask* __restrict_
 //   void entropy(std::vector<STask>&, double* out)
 //   void sample(SampleTable&, const SArgs&)          the snapshot launch of the chunk
 //   void energy(EnergyTable&, const EArgs&, std::vector<double>& coef)   the moment chain launch
+//   void pair(PairTable&, const PArgs&)              the pair chain launch
 
 // dry run: the workspace a chunk would take (256-byte granules, as the arenas)
 struct CountBackend {
@@ -277,6 +285,7 @@ struct CountBackend {
   void energy(EnergyTable& tb, const EArgs&, std::vector<double>& coef) {
     bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()) + al(sizeof(double) * coef.size());
   }
+  void pair(PairTable& tb, const PArgs&) { bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()); }
 };
 
 // everything in one raw device buffer on one stream (the LDS engine's context)
@@ -385,12 +394,23 @@ struct RawBackend {
     std::vector<double> cf = coef;  // (upload takes its vector)
     if (ok()) note(energy_launch(tb, a, cf, st, [&](auto& v) { return upload(v); }));
   }
+  void pair(PairTable& tb, const PArgs& a) {
+    if (ok()) note(pair_launch(tb, a, st, [&](auto& v) { return upload(v); }));
+  }
 };
 
 // ------------------------------------------------------------------ driver
+// whether a backend has the pair chain launch
+template <class BE, class = void>
+struct has_pair : std::false_type {};
+template <class BE>
+struct has_pair<BE, std::void_t<decltype(std::declval<BE&>().pair(std::declval<PairTable&>(), std::declval<const PArgs&>()))>>
+    : std::true_type {};
+
 // close outputs one state can produce (sizes its slice of the result buffer)
 inline size_t max_outputs(int L, int p, int nrows, Want w) {
-  return 1 + (w.env() ? size_t(L) * p : 0) + 2 * size_t(nrows) * L + (w.mom ? size_t(kEnergyOut) : 0);
+  return 1 + (w.env() ? size_t(L) * p : 0) + 2 * size_t(nrows) * L + (w.mom ? size_t(kEnergyOut) : 0) +
+         (w.pair ? pair_outputs(L, p) : 0);
 }
 
 // Queue every launch of one chunk.  out_slot[i] is state i's index in the
@@ -402,10 +422,12 @@ inline size_t max_outputs(int L, int p, int nrows, Want w) {
 // launches form Y = Renv_b[q] S and X = S^H Y, stage B takes the eigenvalues of
 // X (the Schmidt weights of the sector) and one wave per (state, bond) reduces
 // the entropy.  A sector without an Lenv or Renv block gets zero weights.
+// With want.pair S are the bras and kets the kets of the chunk's pairs.
 template <class BE>
 double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc*>& S,
                   const std::vector<size_t>& out_slot, const std::vector<int>& rows, Want want,
-                  std::vector<Dest>& dests, Traffic& tr, Spec* spec = nullptr, Snap* snap = nullptr) {
+                  std::vector<Dest>& dests, Traffic& tr, Spec* spec = nullptr, Snap* snap = nullptr,
+                  const std::vector<const StateDesc*>* kets = nullptr) {
   const int Q1 = Q + 1, B = int(S.size()), R = int(rows.size());
   const bool ada = want.ada && R > 0, nn = want.nn && R > 0, env = want.occ || ada || nn;
   const bool renv = env || spec != nullptr || (snap && !snap->given);
@@ -414,6 +436,11 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
   const double* one = be.one();
   if (want.mom) {
     energy_chunk(be, L, p, Q, S, out_slot, d_out, one, dests, tr);
+    return d_out;
+  }
+  if (want.pair) {
+    if constexpr (has_pair<BE>::value)  // (a backend without the pair launch is never asked for pairs)
+      pair_chunk(be, L, p, Q, S, *kets, out_slot, want.pair_occ, want.pair_hop, d_out, one, dests, tr);
     return d_out;
   }
   auto D = [&](int i, int b, int q) { return (q < 0 || q > Q) ? 0 : S[i]->dims[size_t(b) * Q1 + q]; };
@@ -819,13 +846,16 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
 }
 
 // workspace bytes of every state alone (a chunk of several takes at most the
-// sum), by a dry run per distinct set of bond-sector dims
+// sum), by a dry run per distinct set of bond-sector dims (with kets: of every pair, per distinct dims of both)
 inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vector<StateDesc>& desc,
-                                           const std::vector<int>& rows, Want want, const Snap* snap = nullptr) {
+                                           const std::vector<int>& rows, Want want, const Snap* snap = nullptr,
+                                           const std::vector<StateDesc>* kets = nullptr) {
   std::map<std::vector<int>, size_t> seen;
   std::vector<size_t> need(desc.size());
   for (size_t i = 0; i < desc.size(); ++i) {
-    auto it = seen.find(desc[i].dims);
+    std::vector<int> key = desc[i].dims;
+    if (kets) key.insert(key.end(), (*kets)[i].dims.begin(), (*kets)[i].dims.end());
+    auto it = seen.find(key);
     if (it == seen.end()) {
       CountBackend cb;
       std::vector<Dest> dd;
@@ -836,8 +866,11 @@ inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vecto
         sn = *snap;
         sn.ids = nullptr;
       }
-      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt, want.spec ? &sp : nullptr, snap ? &sn : nullptr);
-      it = seen.emplace(desc[i].dims, cb.bytes).first;
+      std::vector<const StateDesc*> ky;
+      if (kets) ky.push_back(&(*kets)[i]);
+      run_chunk(cb, L, p, Q, {&desc[i]}, {0}, rows, want, dd, tt, want.spec ? &sp : nullptr, snap ? &sn : nullptr,
+                kets ? &ky : nullptr);
+      it = seen.emplace(key, cb.bytes).first;
     }
     need[i] = it->second;
   }
@@ -862,6 +895,10 @@ struct Outputs {
   int L = 0, p = 0, nrows = 0;
   const int* rows = nullptr;
   double* mom = nullptr;  // [nt][7]: alone (ocg_observe_moments)
+  // alone (ocg_observe_pairs), complex: [n] <x|y>, [n][L][p] <x|P_k(n)|y>, [n][L-1][2] the hopping elements
+  double* povl = nullptr;
+  double* pocc = nullptr;
+  double* phop = nullptr;
 };
 
 // what the kernels must compute for the requested outputs (the diagonal of a
@@ -873,6 +910,9 @@ inline Want want_of(const Outputs& o) {
   w.nn = o.nn != nullptr && o.nrows > 0;
   w.occ = o.occ != nullptr || w.ada || w.nn;
   w.mom = o.mom != nullptr;
+  w.pair_occ = o.pocc != nullptr;
+  w.pair_hop = o.phop != nullptr && o.L > 1;
+  w.pair = o.povl != nullptr || w.pair_occ || w.pair_hop;
   return w;
 }
 
@@ -893,6 +933,14 @@ inline void scatter(const std::vector<Dest>& dests, const double* res, const Out
       case 5:
         o.mom[d.idx] = res[2 * j];
         o.mom[d.idx + 1] = res[2 * j + 1];
+        break;
+      case 6:
+      case 7:
+      case 8:
+        if (double* dst = d.kind == 6 ? o.povl : d.kind == 7 ? o.pocc : o.phop) {
+          dst[2 * d.idx] = res[2 * j];
+          dst[2 * d.idx + 1] = res[2 * j + 1];
+        }
         break;
     }
   }

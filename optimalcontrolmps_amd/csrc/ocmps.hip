@@ -1805,14 +1805,14 @@ int ocg_get_state(ocg_ctx* c, int which, int t, int* dims, double* data, size_t 
 // free device memory.  Reads the slots only.
 static constexpr size_t kObsKeepBytes = size_t(256) << 20;
 static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr);
-// With so the spectrum stages run too and their results go to *so; with sn the
-// snapshot launch follows the right sweep instead and its results go to sn's outputs.
-static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                         double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
+                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr,
+                         const std::vector<obs::StateDesc>* kets = nullptr);
+// the block descriptors of pool slots (and the bond dimensions into entry out0 + i of bond)
+static int slot_descs(ocg_ctx* c, const std::vector<int>& slots, size_t out0, int* bond,
+                      std::vector<obs::StateDesc>& desc) {
   const OcgParams& P = c->P;
   const int nst = int(slots.size());
-  std::vector<obs::StateDesc> desc(nst);
+  desc.assign(nst, obs::StateDesc{});
   // the dims of the slot range in one copy (a trajectory's slots are neighbours)
   const int s0 = *std::min_element(slots.begin(), slots.end()), s1 = *std::max_element(slots.begin(), slots.end());
   std::vector<int> hd(size_t(s1 - s0 + 1) * P.nsq);
@@ -1843,21 +1843,39 @@ static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0,
         bond[(out0 + i) * (P.L + 1) + b] = sum;
       }
   }
+  return 0;
+}
+// With so the spectrum stages run too and their results go to *so; with sn the
+// snapshot launch follows the right sweep instead and its results go to sn's outputs.
+static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
+                         double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
+  std::vector<obs::StateDesc> desc;
+  if (int rc = slot_descs(c, slots, out0, bond, desc)) return rc;
   return observe_descs(c, desc, out0, o, occ_buf, so, sn);
 }
 
-// the chunks of observe.hpp's driver over states described on the device
+// the chunks of observe.hpp's driver over states described on the device (with kets: over the pairs
+// bra desc[i], ket (*kets)[i])
 static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn) {
+                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn,
+                         const std::vector<obs::StateDesc>* kets) {
   const OcgParams& P = c->P;
   const int nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !sn) return 0;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !sn) return 0;
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
     if (wo > obs::kSampleMaxOrder) return fail(c, OCG_ECAP, "snapshots: a bond sector above order 512");
+  }
+  if (want.pair) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) {
+      obs::widest(desc[i], P.L, P.Q1, wb, wo);
+      obs::widest((*kets)[i], P.L, P.Q1, wb, wo);
+    }
+    if (wo > obs::kPairMaxOrder) return fail(c, OCG_ECAP, "pairs: a bond sector above order 512");
   }
   if (want.mom) {
     int wb = 0, wo = 0;
@@ -1873,19 +1891,21 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     if (wo > obs::kEigMaxOrder) return fail(c, OCG_ECAP, "spectrum: a bond sector above order 512");
   }
   const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want, sn);
+  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want, sn, kets);
   const size_t budget = obs::chunk_budget();
   for (int i0 = 0; i0 < nst;) {
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : "moments") + ": the workspace of one state (" +
+    if ((sn || want.mom || want.pair) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : want.pair ? "pairs" : "moments") +
+                                     ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
                                      std::to_string(sum) + " B) exceeds the chunk budget");
-    std::vector<const obs::StateDesc*> S;
+    std::vector<const obs::StateDesc*> S, SY;
     std::vector<size_t> os;
     for (int i = i0; i < i1; ++i) {
       S.push_back(&desc[i]);
+      if (kets) SY.push_back(&(*kets)[i]);
       os.push_back(out0 + i);
     }
     obs::RawBackend be;
@@ -1918,7 +1938,8 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     std::vector<int> status;
     obs::Spec sp;
     if (!rc) {
-      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr, sn);
+      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr, sn,
+                                           kets ? &SY : nullptr);
       if (sn && be.ok()) be.note(sn->fetch(out0 + i0, S.size(), P.L, c->stream));
       res.resize(2 * std::max<size_t>(dests.size(), 1));
       if (be.ok() && !dests.empty())
@@ -2002,15 +2023,20 @@ static int staged_check(ocg_ctx* c, int n, const int* dims, int wcap) {
 // itself: its blocks are the contiguous row-major matrices the descriptors want, and a
 // sector may be larger than the Schmidt-rank bound of the pool slots (a padded or
 // over-parametrised state).
+// With dims_y / data_y the states are the bras of pairs and those the kets, staged behind them.
 static int observe_staged(ocg_ctx* c, int n, const int* dims, const double* const* data, const obs::Outputs& o,
-                          const obs::SpecOutputs* so, obs::Snap* sn, const char* what) {
+                          const obs::SpecOutputs* so, obs::Snap* sn, const char* what, const int* dims_y = nullptr,
+                          const double* const* data_y = nullptr) {
   const OcgParams& P = c->P;
   const int B = std::min(n, 64);
   for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb = std::min(B, n - i0);
+    const int nb0 = std::min(B, n - i0), nb = dims_y ? 2 * nb0 : nb0;
+    // entry i of the batch: state i0 + i, or for i >= nb0 the ket i0 + i - nb0
+    auto dims_of = [&](int i) { return i < nb0 ? dims + size_t(i0 + i) * P.nsq : dims_y + size_t(i0 + i - nb0) * P.nsq; };
+    auto data_of = [&](int i) { return i < nb0 ? data[i0 + i] : data_y[i0 + i - nb0]; };
     std::vector<obs::StateDesc> desc(nb);
     std::vector<size_t> at(nb + 1, 0);
-    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims + size_t(i0 + i) * P.nsq);
+    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims_of(i));
     double* d_st = nullptr;
     if (hipMalloc((void**)&d_st, 16 * std::max<size_t>(at[nb], 1)) != hipSuccess) {
       (void)hipGetLastError();
@@ -2018,12 +2044,17 @@ static int observe_staged(ocg_ctx* c, int n, const int* dims, const double* cons
     }
     hipError_t e = hipSuccess;
     for (int i = 0; i < nb && e == hipSuccess; ++i) {
-      const int* d = dims + size_t(i0 + i) * P.nsq;
+      const int* d = dims_of(i);
       if (at[i + 1] > at[i])
-        e = hipMemcpyAsync(d_st + 2 * at[i], data[i0 + i], 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
+        e = hipMemcpyAsync(d_st + 2 * at[i], data_of(i), 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
       obs::compact_desc(P.L, P.p, P.Q, d, d_st + 2 * at[i], desc[i]);
     }
-    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, so, sn)
+    std::vector<obs::StateDesc> kets;
+    if (dims_y) {
+      kets.assign(desc.begin() + nb0, desc.end());
+      desc.resize(nb0);
+    }
+    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, so, sn, dims_y ? &kets : nullptr)
                              : fail(c, OCG_EHIP, std::string(what) + ": " + hipGetErrorString(e));
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(d_st);
@@ -2252,6 +2283,41 @@ int ocg_observe_moments_states(ocg_ctx* c, int n, const int* dims, const double*
   obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
   o.mom = mom;
   return observe_staged(c, n, dims, data, o, nullptr, nullptr, "moments");
+}
+
+int ocg_observe_pairs(ocg_ctx* c, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
+                      double* occ, double* hop) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_pairs(c->hbm, which_x, tx, which_y, ty, npairs, ovl, occ, hop));
+  std::vector<int> sx, sy;
+  if (int rc = trajectory_slots(c, which_x, tx, npairs, sx, nullptr)) return rc;
+  if (int rc = trajectory_slots(c, which_y, ty, npairs, sy, nullptr)) return rc;
+  if (npairs == 0 || (!ovl && !occ && !hop)) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.povl = ovl;
+  o.pocc = occ;
+  o.phop = hop;
+  std::vector<obs::StateDesc> dx, dy;
+  if (int rc = slot_descs(c, sx, 0, nullptr, dx)) return rc;
+  if (int rc = slot_descs(c, sy, 0, nullptr, dy)) return rc;
+  return observe_descs(c, dx, 0, o, nullptr, nullptr, nullptr, &dy);
+}
+
+int ocg_observe_pairs_states(ocg_ctx* c, int n, const int* dims_x, const double* const* x, const int* dims_y,
+                             const double* const* y, double* ovl, double* occ, double* hop) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_pairs_states(c->hbm, n, dims_x, x, dims_y, y, ovl, occ, hop));
+  if (n < 0 || (n > 0 && (!dims_x || !x || !dims_y || !y))) return fail(c, OCG_EINVAL, "bad argument");
+  if (n == 0 || (!ovl && !occ && !hop)) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = staged_check(c, n, dims_x, -1)) return rc;
+  if (int rc = staged_check(c, n, dims_y, -1)) return rc;
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.povl = ovl;
+  o.pocc = occ;
+  o.phop = hop;
+  return observe_staged(c, n, dims_x, x, o, nullptr, nullptr, "pairs", dims_y, y);
 }
 
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,

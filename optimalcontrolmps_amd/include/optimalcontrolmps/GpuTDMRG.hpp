@@ -373,6 +373,40 @@ class GpuTDMRG::Engine {
                   "ocg_observe_moments");
     return o;
   }
+  // Transition matrix elements between states of the device-resident trajectories
+  // (ocg_observe_pairs): pair e has the bra state tx[e] of which_x and the ket state ty[e] of
+  // which_y (0 psi_t, 1 xi_t, 2 xiH_t; both empty: all N times, t with t).
+  PairObservables observePairs(int which_x, const std::vector<int>& tx, int which_y, const std::vector<int>& ty) {
+    PairObservables o;
+    o.L = stepper.L;
+    o.p = stepper.p;
+    o.tx = tx;
+    o.ty = ty;
+    if (tx.empty() && ty.empty())
+      for (size_t t = 0; t < N; ++t) {
+        o.tx.push_back(int(t));
+        o.ty.push_back(int(t));
+      }
+    if (o.tx.size() != o.ty.size()) throw std::invalid_argument("observePairs: tx and ty differ in length");
+    const size_t n = o.tx.size();
+    o.ovl.assign(n, Cplx(0, 0));
+    o.occ.assign(n * o.L * o.p, Cplx(0, 0));
+    o.hop.assign(n * 2 * (o.L - 1), Cplx(0, 0));
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_observe_pairs(c, which_x, o.tx.data(), which_y, o.ty.data(), int(n),
+                                    reinterpret_cast<double*>(o.ovl.data()), reinterpret_cast<double*>(o.occ.data()),
+                                    reinterpret_cast<double*>(o.hop.data())),
+                  c, "ocg_observe_pairs");
+    return o;
+  }
+  // launches of one ocg_kernel_stats kind on shard 0 since the context was created (diagnostics: kind 0
+  // counts the trajectory propagations)
+  long kernelLaunches(int kind) {
+    long n = 0;
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_kernel_stats(c, kind, nullptr, &n, nullptr, nullptr, nullptr), c, "ocg_kernel_stats");
+    return n;
+  }
   std::vector<MPS> psiTrajectory() {
     std::vector<MPS> out;
     for (size_t t = 0; t < N; ++t)

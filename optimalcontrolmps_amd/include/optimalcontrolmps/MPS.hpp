@@ -98,6 +98,47 @@ struct TrajectoryEnergies {
   std::vector<double> energy, variance;  // [e]
 };
 
+// Transition matrix elements between stored states (ocg_observe_pairs): per pair e of a bra x
+// (state tx[e]) and a ket y (state ty[e]) the raw numbers <x|y>, <x|P_k(n)|y> and the hopping
+// elements <x|a+_b a_{b+1}|y>, <x|a_b a+_{b+1}|y> (none divided by a norm).
+struct PairObservables {
+  int L = 0, p = 0;
+  std::vector<int> tx, ty;  // [e] state indices
+  std::vector<Cplx> ovl;    // [e]
+  std::vector<Cplx> occ;    // [e][L][p]
+  std::vector<Cplx> hop;    // [e][L-1][2]
+  size_t size() const { return tx.size(); }
+  // <x|n_k|y>, k = 1..L
+  Cplx number(size_t e, int k) const {
+    Cplx s = 0;
+    for (int n = 0; n < p; ++n) s += double(n) * occ[(e * L + (k - 1)) * p + n];
+    return s;
+  }
+  // <x|D|y>, D = sum_k n_k (n_k - 1) / 2
+  Cplx interaction(size_t e) const {
+    Cplx s = 0;
+    for (int k = 0; k < L; ++k)
+      for (int n = 0; n < p; ++n) s += 0.5 * n * (n - 1.0) * occ[(e * L + k) * p + n];
+    return s;
+  }
+  // <x|K|y>, K = sum_b (a+_b a_{b+1} + a_b a+_{b+1})
+  Cplx hopping(size_t e) const {
+    Cplx s = 0;
+    for (int j = 0; j < 2 * (L - 1); ++j) s += hop[e * 2 * (L - 1) + j];
+    return s;
+  }
+};
+// First-order sensitivities of the cost to the controls on the time grid
+// (OptimalControl::getControlSensitivities): tstep Re(i <xi_t|dH/dlambda|psi_t> F) for
+// lambda = U (dH = D, the fidelity gradient), J (dH = -K) and a site potential eps_k (dH = n_k);
+// overlap[t] = <xi_t|psi_t>, constant in t for exact unitary evolution.  A total over t takes
+// trapezoid weights (1/2 at t = 0 and t = N - 1).
+struct ControlSensitivities {
+  stdvec dU, dJ;              // [t]
+  rowmat dEps;                // [t][k]
+  std::vector<Cplx> overlap;  // [t]
+};
+
 // Observables of nt trajectory states evaluated on the device (ocg_observe,
 // ocg_observe_spectrum, include/ocmps.h): what GpuTDMRG::Engine::observe and
 // OptimalControl::getPsitObservables return and the overloads of

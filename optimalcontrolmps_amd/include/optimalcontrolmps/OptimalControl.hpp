@@ -17,6 +17,7 @@
 //           sample(which, ts, nshots, seed), fockAmplitudes(which, ts, configs) (optional: samplePsit,
 //           getPsitFockProbability),
 //           observeMoments(which, ts) (optional: getPsitEnergies, with the stepper's hopping()),
+//           observePairs(which_x, tx, which_y, ty) (optional: getControlSensitivities),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -107,6 +108,38 @@ class OptimalControl {
       r.variance.push_back(r.moments.energyVariance(t, J, u[t]));
     }
     return r;
+  }
+  // First-order sensitivities of the fidelity cost to U(t) (the fidelity gradient itself), to the
+  // hopping J(t) and to a site potential eps_k(t), and the overlap <xi_t|psi_t>, on the time grid:
+  // tstep Re(i <xi_t|dH/dlambda|psi_t> F), the reference's gradient formula (:240-246) with
+  // dH/dJ = -K and dH/deps_k = n_k, so with its time discretisation: a total over t takes trapezoid
+  // weights.  GROUP coefficients are converted to the time grid first and the results are not
+  // projected back onto the basis.  Makes psi, xi and divT available exactly as the non-BFGS gradient
+  // does (new_control = false after a gradient propagates nothing), then reads the device
+  // trajectories (Engine::observePairs).  Only for steppers whose Engine has observePairs() (GpuTDMRG).
+  ocmps::ControlSensitivities getControlSensitivities(const stdvec& control, const bool new_control = true) {
+    const stdvec u = GRAPE ? control : basis.convertControl(control, new_control);
+    if (u.size() != N) throw std::invalid_argument("getControlSensitivities: control has the wrong length");
+    if (new_control) {
+      calculatedXi = false;
+      calcPsiXiDivT(u);
+    }
+    if (!calculatedXi) {
+      calcXi(u);
+      calcDivT();
+    }
+    const Cplx F = engine->overlapFactor(), I(0, 1);
+    const ocmps::PairObservables pr = engine->observePairs(1, {}, 0, {});
+    ocmps::ControlSensitivities s;
+    for (size_t t = 0; t < N; ++t) {
+      s.dU.push_back(tstep * (I * pr.interaction(t) * F).real());
+      s.dJ.push_back(tstep * (I * (-pr.hopping(t)) * F).real());
+      stdvec e;
+      for (int k = 1; k <= pr.L; ++k) e.push_back(tstep * (I * pr.number(t, k) * F).real());
+      s.dEps.push_back(e);
+      s.overlap.push_back(pr.ovl[t]);
+    }
+    return s;
   }
   size_t getM() const { return M; }
   size_t getN() const { return N; }

@@ -45,9 +45,9 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
                   "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
-                  "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp"],
+                  "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp"],
         "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
-                "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp"],
+                "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -138,6 +138,8 @@ SIGNATURES = [
     ("ocg_fock_amplitudes_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), bp, C.c_int, dp]),
     ("ocg_observe_moments", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, dp]),
     ("ocg_observe_moments_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), dp]),
+    ("ocg_observe_pairs", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, ip, C.c_int, dp, dp, dp]),
+    ("ocg_observe_pairs_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), ip, C.POINTER(dp), dp, dp, dp]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -204,6 +206,23 @@ def energy_variance(mom, J, U):
     mom = np.asarray(mom, np.float64)
     return (J * J * mom[..., 3] - 2 * J * U * mom[..., 5] + U * U * mom[..., 4]) / mom[..., 0] \
         - energy(mom, J, U) ** 2
+
+
+def control_sensitivities(pairs, F, tstep):
+    """First-order sensitivities of the cost 0.5 (1 - |F|^2) to the controls at every time step, from
+    pairs = Engine.observe_pairs(1, None, 0, None) (bra xi_t, ket psi_t) and F = Engine.overlap_factor():
+    dU[t] = tstep Re(i <xi_t|D|psi_t> F) (the gradient of Engine.gradient), dJ[t] = tstep Re(i (-<xi_t|K|psi_t>) F)
+    for H = -J K + U D, dEps[t][k] = tstep Re(i <xi_t|n_k|psi_t> F) for a site potential sum_k eps_k n_k, and
+    overlap[t] = <xi_t|psi_t> (independent of t for exact unitary evolution: its drift measures the truncation).
+    They carry the time discretisation of the gradient formula: a total over t takes trapezoid weights (1/2 at
+    t = 0 and t = N - 1)."""
+    occ, hop, F = np.asarray(pairs["occ"]), np.asarray(pairs["hop"]), complex(F)
+    n = np.arange(occ.shape[-1])
+    nk = (occ * n).sum(-1)
+    D = (occ * (n * (n - 1) / 2)).sum((-1, -2))
+    K = hop.sum((-1, -2))
+    return {"dU": tstep * (1j * D * F).real, "dJ": tstep * (1j * (-K) * F).real,
+            "dEps": tstep * (1j * nk * F).real, "overlap": np.asarray(pairs["ovl"]).copy()}
 
 
 class Engine:
@@ -646,6 +665,47 @@ class Engine:
         dims, raws, data = self._staged(states)
         self._chk(lib().ocg_observe_moments_states(self.h, n, dims.ctypes.data_as(ip), data, out.ctypes.data_as(dp)),
                   "ocg_observe_moments_states")
+        return out
+
+    PAIR_OUTPUTS = ("ovl", "occ", "hop")
+
+    def _pairs_out(self, n, outputs):
+        bad = set(outputs) - set(self.PAIR_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown pair outputs {sorted(bad)}")
+        L, p = self.L, self.p
+        full = {"ovl": (n,), "occ": (n, L, p), "hop": (n, L - 1, 2)}
+        out = {k: np.zeros(full[k], np.complex128) for k in self.PAIR_OUTPUTS if k in outputs}
+        return out, [out[k].ctypes.data_as(dp) if k in out else None for k in self.PAIR_OUTPUTS]
+
+    def observe_pairs(self, which_x, tx, which_y, ty, outputs=PAIR_OUTPUTS):
+        """Transition matrix elements between device trajectory states (ocg_observe_pairs): pair e has the
+        bra state tx[e] of trajectory which_x and the ket state ty[e] of which_y (0 psi_t, 1 xi_t, 2 xiH_t;
+        None: 0..n-1).  Returns a dict of complex arrays, raw (not divided by any norm): ovl (n,) = <x|y>,
+        occ (n, L, p) = <x|P_k(n)|y> and hop (n, L-1, 2) = <x|a+_b a_{b+1}|y>, <x|a_b a+_{b+1}|y>.
+        `outputs` selects a subset: what is left out is not computed."""
+        n = self.N if tx is None and ty is None else len(tx if tx is not None else ty)
+        ax, px = (None, None) if tx is None else _i(list(tx))
+        ay, py = (None, None) if ty is None else _i(list(ty))
+        if ax is not None and ay is not None and len(ax) != len(ay):
+            raise ValueError("tx and ty differ in length")
+        out, ptrs = self._pairs_out(n, outputs)
+        self._chk(lib().ocg_observe_pairs(self.h, int(which_x), px, int(which_y), py, n, *ptrs), "ocg_observe_pairs")
+        return out
+
+    def observe_pairs_states(self, xs, ys, outputs=PAIR_OUTPUTS):
+        """observe_pairs() for caller-supplied host states of any gauge or norm: pair e is (xs[e], ys[e])
+        (ocg_observe_pairs_states)."""
+        if len(xs) != len(ys):
+            raise ValueError("xs and ys differ in length")
+        n = len(xs)
+        out, ptrs = self._pairs_out(n, outputs)
+        if n == 0:
+            return out
+        dx, rx, datx = self._staged(xs)
+        dy, ry, daty = self._staged(ys)
+        self._chk(lib().ocg_observe_pairs_states(self.h, n, dx.ctypes.data_as(ip), datx, dy.ctypes.data_as(ip), daty,
+                                                 *ptrs), "ocg_observe_pairs_states")
         return out
 
     def stats(self, kind):

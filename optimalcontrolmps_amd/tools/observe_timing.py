@@ -2,7 +2,7 @@
 was before: one ocg_get_state copy per state (a lower bound of that path, which
 adds the host contraction of correlations.hpp on top).
 
-    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|e1|e4|all] [--reps R] [--out DIR]
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|e1|e4|pairs|all] [--reps R] [--out DIR]
 
 One process; every shape is warmed up; each timed call ends in a device
 synchronise (both entry points return only after their results are on the
@@ -32,6 +32,12 @@ only other route to <H^2> (copy every state out and contract on the host); at
 config 1 the chain kernel also alternates with the forced task-list path
 (OCG_OBS_ENERGY_CHAIN=0).  Writes observe_energy_config1.json /
 observe_energy_config4.json.
+
+pairs: the transition elements (ocg_observe_pairs) of all (xi_t, psi_t) at config 1,
+N_t = 201: the chain kernel, the forced task-list path (OCG_OBS_PAIR_CHAIN=0) and
+the host route (ocg_get_state of both trajectories plus the numpy block
+contraction of tests/pair_reference.py), alternating.  Writes
+observe_pairs_config1.json.
 """
 from __future__ import annotations
 
@@ -358,9 +364,59 @@ def energy4(reps):
     return res
 
 
+def pairs1(reps):
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pair_reference as P
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    eng.propagate(np.linspace(2.5, 50.0, Nt), 3)
+
+    def forced_lists():
+        os.environ["OCG_OBS_PAIR_CHAIN"] = "0"
+        try:
+            return eng.observe_pairs(1, None, 0, None)
+        finally:
+            del os.environ["OCG_OBS_PAIR_CHAIN"]
+
+    def host_route():
+        out = []
+        for t in range(Nt):
+            x, y = eng.state(1, t), eng.state(0, t)
+            out.append(P.pairs_ref(x.dims, x.data, y.dims, y.data, L, p, Q))
+        return out
+    cases = {"pairs": lambda: eng.observe_pairs(1, None, 0, None), "pairs_lists": forced_lists}
+    for f in cases.values():
+        f()
+        f()
+    t = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, f in cases.items():
+            t[k].append(timed(f))
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine, all (xi_t, psi_t)",
+           "sector_max": int(max(eng.state(w, t).dims.max() for w in (0, 1) for t in (0, Nt // 2, Nt - 1)))}
+    res.update({k: spread(v) for k, v in t.items()})
+    host_route()
+    res["host_get_state_plus_numpy"] = spread([timed(host_route) for _ in range(max(2, reps // 8))])
+    for k in cases:
+        eng.reset_stats()
+        cases[k]()
+        res[k + "_kind9"] = eng.stats(9)
+        res[k + "_vs_host"] = res["host_get_state_plus_numpy"]["median_ms"] / res[k]["median_ms"]
+    res["chain_vs_lists"] = res["pairs_lists"]["median_ms"] / res["pairs"]["median_ms"]
+    a, b, h = cases["pairs"](), forced_lists(), host_route()
+    res["chain_lists_max_dev"] = float(max(np.abs(a[k] - b[k]).max() for k in a))
+    res["chain_host_max_dev"] = float(max(np.abs(a[k] - np.array([r[k] for r in h])).max() for k in a))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "e1", "e4", "all"])
+    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "e1", "e4", "pairs", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
@@ -368,13 +424,14 @@ def main():
     for name, fn, reps in (("1", config1, a.reps), ("4", config4, max(3, a.reps // 4)),
                            ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4)),
                            ("p1", sample1, a.reps), ("p4", sample4, max(3, a.reps // 4)),
-                           ("e1", energy1, a.reps), ("e4", energy4, max(3, a.reps // 4))):
+                           ("e1", energy1, a.reps), ("e4", energy4, max(3, a.reps // 4)),
+                           ("pairs", pairs1, a.reps)):
         if a.config in (name, "all"):
             res = fn(reps)
             res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
             kind = {"s": "observe_spectrum_config", "p": "observe_sample_config",
                     "e": "observe_energy_config"}.get(name[0], "observe_config")
-            out = f"{kind}{name[-1]}.json"
+            out = "observe_pairs_config1.json" if name == "pairs" else f"{kind}{name[-1]}.json"
             with open(os.path.join(a.out, out), "w") as f:
                 json.dump(res, f, indent=1)
             print(json.dumps(res))
