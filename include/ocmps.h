@@ -85,7 +85,8 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * 5 ocg_observe_spectrum, ocg_observe_spectrum_states;
  * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states;
  * 7 ocg_observe_moments, ocg_observe_moments_states; added within 7 (no existing
- * entry point or struct changed): ocg_observe_pairs, ocg_observe_pairs_states. */
+ * entry point or struct changed): ocg_observe_pairs, ocg_observe_pairs_states;
+ * ocg_observe_strings, ocg_observe_strings_states. */
 #define OCG_ABI_VERSION 7
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
@@ -376,6 +377,43 @@ int ocg_observe_pairs(ocg_ctx* ctx, int which_x, const int* tx, int which_y, con
 int ocg_observe_pairs_states(ocg_ctx* ctx, int n, const int* dims_x, const double* const* x, const int* dims_y,
                              const double* const* y, double* ovl, double* occ, double* hop);
 
+/* Expectations of products of diagonal one-site operators (string operators) in stored
+ * states: parity (string) order, the counting statistics of a block, multi-point
+ * projector correlators.  f[nops][L][p][2] are complex tables, interleaved (re, im);
+ * operator m is O_m = (x)_k F_{m,k} with F_{m,k} = sum_n f[m][k-1][n] P_k(n), P_k(n) the
+ * projector on occupation n of site k (the projector of ocg_observe_pairs).
+ *   out[nt][nops][2] = <s|O_m|s>, complex, raw (not divided by <s|s>), gauge free, any norm.
+ * which, ts (NULL: 0..nt-1; repeats and any order are fine), existence rules and
+ * OCG_ESTATE / OCG_EINVAL as ocg_observe.  nops == 0 or nt == 0 writes nothing.
+ * OCG_EINVAL: nops < 0, f == NULL with nops > 0, a table entry that is not finite.
+ *
+ * The numbers.  The support [a, b] of operator m runs from its first to its last site
+ * whose table is not exactly (1, 0) for every n.  With an empty support out = norm2.
+ * Otherwise, with Lenv / Renv the environments of ocg_observe and A_k(q, n) block (q, n)
+ * of site k,
+ *   E_{a-1}[q] = Lenv_{a-1}[q]
+ *   E_k[q+n]  += f[k][n] A_k(q,n)^H E_{k-1}[q] A_k(q,n)        k = a..b
+ *   out        = sum_q sum E_b[q] o Renv_b[q]^T                 (= sum_q tr(E_b[q] Renv_b[q])).
+ * A block that does not exist contributes nothing: the level cut (p - 1 < Q), empty
+ * sectors, sectors of dims with no block.  The work per operator is proportional to its
+ * support length, not to L; Lenv and Renv are formed once per state, however many
+ * operators there are.
+ *
+ * Bond sectors of order up to 512 (OCG_ECAP above).  Chunking and OCG_OBS_BUDGET as
+ * ocg_observe_moments (OCG_ENOMEM if the workspace of one state with all its operators
+ * exceeds the chunk budget).  States whose sectors are all at most 16 wide run in two
+ * kernels per chunk, whatever nops and nt are (OCG_OBS_STRING_CHAIN=0: the task-list path
+ * for all, 2 (L - 1) + 2 M + 1 launches per chunk with M the longest support, an empty
+ * one counting 1; the two paths agree to rounding, not bit for bit).  <s|O_m|s> depends
+ * on s, on table m and on the path alone: bit-identical whatever other operators or
+ * states are requested, in whatever order, and however the request is chunked.  Reads
+ * the trajectories only.  Counted in ocg_kernel_stats kind 9. */
+int ocg_observe_strings(ocg_ctx* ctx, int which, const int* ts, int nt, const double* f, int nops, double* out);
+/* The same for n caller-supplied host states (any gauge or norm, zero-padded sectors
+ * allowed), staged on the device in batches as ocg_observe_pairs_states. */
+int ocg_observe_strings_states(ocg_ctx* ctx, int n, const int* dims, const double* const* data, const double* f,
+                               int nops, double* out);
+
 /* ControlBasis::convertHessian (src/ControlBasis.cpp:91-116) on the device:
  * Hc (M x M) = V Hu V^T with Hu row-major N x N (host), V row-major M x N
  * (V[n][i] = S_i f_{i n}, the transposed control Jacobian).  Each entry is a
@@ -411,7 +449,8 @@ int ocg_denmat_decomp(ocg_ctx* ctx, int nm, const int* rows, const int* cols, co
  * *alg_flops = trajectory-checkpointed getHessians completed, *alg_bytes = the
  * segment length of the last one), 9 the observable kernels of ocg_observe /
  * ocg_observe_states / ocg_observe_spectrum[_states] / ocg_sample[_states] /
- * ocg_fock_amplitudes[_states] / ocg_observe_moments[_states] / ocg_observe_pairs[_states] (HIP-event time of their chunks, kernel launches, and the
+ * ocg_fock_amplitudes[_states] / ocg_observe_moments[_states] / ocg_observe_pairs[_states] /
+ * ocg_observe_strings[_states] (HIP-event time of their chunks, kernel launches, and the
  * algorithmic bytes and flops of the host-built task lists).  Sums since the
  * last reset. */
 int ocg_kernel_stats(ocg_ctx* ctx, int kind, double* total_ms, long* launches, double* alg_bytes,

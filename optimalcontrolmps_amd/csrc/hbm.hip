@@ -3212,6 +3212,10 @@ struct ObsBackend {
   void pair(obs::PairTable& tb, const obs::PArgs& a) {
     HCK(obs::pair_launch(tb, a, E.st, [&](auto& v) { return E.upload(v); }));
   }
+  const double* consts(std::vector<double>& v) { return E.upload(v); }
+  void string(obs::StringTable& tb, const obs::StrArgs& a) {
+    HCK(obs::string_launch(tb, a, E.st, [&](auto& v) { return E.upload(v); }));
+  }
 };
 
 obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
@@ -3261,7 +3265,12 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
   const int L = E.L, nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !sn) return;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !want.str && !sn) return;
+  if (want.str) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
+    if (wo > obs::kStringMaxOrder) throw hbm::Error(2, "strings: a bond sector above order 512");
+  }
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
@@ -3295,8 +3304,8 @@ void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom || want.pair) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      throw hbm::Error(6, std::string(sn ? "snapshots" : want.pair ? "pairs" : "moments") +
+    if ((sn || want.mom || want.pair || want.str) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      throw hbm::Error(6, std::string(sn ? "snapshots" : want.pair ? "pairs" : want.str ? "strings" : "moments") +
                               ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
                               std::to_string(sum) + " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S, SY;
@@ -3687,6 +3696,51 @@ int hbm_observe_pairs_states(hbm_engine* h, int n, const int* dims_x, const doub
     o.pocc = occ;
     o.phop = hop;
     observe_staged(h, n, dims_x, x, o, nullptr, nullptr, dims_y, y);
+  });
+}
+
+namespace {
+// the operators of a string request (f[nops][L][p][2], all finite) with their supports
+void string_request(const hbm::Engine& E, const double* f, int nops, obs::Strings& sr) {
+  if (nops < 0 || (nops > 0 && !f)) throw hbm::Error(1, "bad operator tables");
+  const size_t nf = 2 * size_t(nops) * E.L * E.p;
+  for (size_t j = 0; j < nf; ++j)
+    if (!std::isfinite(f[j])) throw hbm::Error(1, "a table entry is not finite");
+  sr.nops = nops;
+  sr.f = f;
+  sr.prepare(E.L, E.p);
+}
+}  // namespace
+
+int hbm_observe_strings(hbm_engine* h, int which, const int* ts, int nt, const double* f, int nops, double* out) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
+    obs::Strings sr;
+    string_request(E, f, nops, sr);
+    if (nt == 0 || nops == 0) return;
+    if (!out) throw hbm::Error(1, "bad output");
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.str = &sr;
+    o.sout = out;
+    observe_slots(h, slots, 0, o, nullptr, nullptr);
+  });
+}
+
+int hbm_observe_strings_states(hbm_engine* h, int n, const int* dims, const double* const* data, const double* f,
+                               int nops, double* out) {
+  return guard(h, [&] {
+    hbm::Engine& E = *h->E;
+    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
+    obs::Strings sr;
+    string_request(E, f, nops, sr);
+    if (n == 0 || nops == 0) return;
+    if (!out) throw hbm::Error(1, "bad output");
+    staged_check(E, n, dims, -1);
+    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
+    o.str = &sr;
+    o.sout = out;
+    observe_staged(h, n, dims, data, o, nullptr, nullptr);
   });
 }
 

@@ -87,6 +87,10 @@ int hbm_observe_pairs(hbm_engine* h, int which_x, const int* tx, int which_y, co
                       double* occ, double* hop);
 int hbm_observe_pairs_states(hbm_engine* h, int n, const int* dims_x, const double* const* x, const int* dims_y,
                              const double* const* y, double* ovl, double* occ, double* hop);
+// ocg_observe_strings / ocg_observe_strings_states (observe_string.hpp)
+int hbm_observe_strings(hbm_engine* h, int which, const int* ts, int nt, const double* f, int nops, double* out);
+int hbm_observe_strings_states(hbm_engine* h, int n, const int* dims, const double* const* data, const double* f,
+                               int nops, double* out);
 // kinds 0-6 as ocg_kernel_stats (HIP-event phase times); 7: the MFMA GEMM
 // kernel (k_gemm) with its algorithmic bytes and flops; 9: the observable kernels
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps);

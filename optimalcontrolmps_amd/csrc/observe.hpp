@@ -19,6 +19,8 @@
 // With Want::pair the chunk is a list of (bra, ket) pairs and runs observe_pair.hpp's
 // transition sweeps (ocg_observe_pairs).
 //
+// With Want::str the chunk runs observe_string.hpp's string-operator sweeps (ocg_observe_strings).
+//
 // With a Spec the spectrum stages follow the sweeps (ocg_observe_spectrum):
 // the Schmidt weights and entropies of every bond from Lenv_b and Renv_b on
 // observe_eig.hpp's batched Jacobi eigensolver (see run_chunk).
@@ -84,6 +86,7 @@ struct Want {
   bool spec = false;  // Schmidt weights and entropies of every bond (run_chunk's Spec argument)
   bool mom = false;   // the energy moments alone (observe_energy.hpp)
   bool pair = false, pair_occ = false, pair_hop = false;  // transition elements of pairs alone (observe_pair.hpp)
+  const struct Strings* str = nullptr;                    // string-operator expectations alone (observe_string.hpp)
   bool env() const { return occ || ada || nn; }
 };
 // the spectrum results of one chunk (device addresses, valid until the chunk's sync)
@@ -119,7 +122,7 @@ struct Snap {
   double* d_val = nullptr;                  // device: logp [state][nper], or amplitudes [state][nper][2]
 };
 // where a close result goes: kind 0 norm2, 1 occ, 2 ada (complex), 3 nn, 4 a real moment, 5 <K D> (complex),
-// 6 / 7 / 8 a pair's ovl / occ / hop (complex)
+// 6 / 7 / 8 a pair's ovl / occ / hop (complex), 9 a string-operator expectation (complex)
 struct Dest {
   int kind;
   size_t idx;
@@ -133,6 +136,7 @@ struct Traffic {
 
 #include "observe_energy.hpp"
 #include "observe_pair.hpp"
+#include "observe_string.hpp"
 
 namespace obs {
 
@@ -244,6 +248,8 @@ __global__ __launch_bounds__(kCloseNT) void k_obs_close(const CTask* __restrict_
 //   void sample(SampleTable&, const SArgs&)          the snapshot launch of the chunk
 //   void energy(EnergyTable&, const EArgs&, std::vector<double>& coef)   the moment chain launch
 //   void pair(PairTable&, const PArgs&)              the pair chain launch
+//   const double* consts(std::vector<double>&)       doubles placed on the device (valid until the chunk's sync)
+//   void string(StringTable&, const StrArgs&)        the two string chain launches
 
 // dry run: the workspace a chunk would take (256-byte granules, as the arenas)
 struct CountBackend {
@@ -286,6 +292,14 @@ struct CountBackend {
     bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()) + al(sizeof(double) * coef.size());
   }
   void pair(PairTable& tb, const PArgs&) { bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()); }
+  const double* consts(std::vector<double>& v) {
+    bytes += al(sizeof(double) * v.size());
+    return reinterpret_cast<const double*>(size_t(256));
+  }
+  void string(StringTable& tb, const StrArgs&) {
+    bytes += al(sizeof(EBlk) * tb.blk.size()) + al(sizeof(int) * tb.dims.size()) + al(sizeof(double) * tb.f.size()) +
+             al(sizeof(int) * tb.sup.size());
+  }
 };
 
 // everything in one raw device buffer on one stream (the LDS engine's context)
@@ -315,7 +329,12 @@ struct RawBackend {
     auto h = std::make_shared<std::vector<T>>(std::move(v));
     v.clear();
     keep.push_back(h);
-    note(hipMemcpyAsync(d, h->data(), sizeof(T) * h->size(), hipMemcpyHostToDevice, st));
+    // in pieces: one copy of a large pageable list takes the runtime tens of milliseconds of host time
+    // (measured: a flat 28 ms once the task lists of a launch pass roughly 0.6 MiB), pieces of this size do not
+    const size_t bytes = sizeof(T) * h->size(), piece = size_t(256) << 10;
+    for (size_t o = 0; o < bytes; o += piece)
+      note(hipMemcpyAsync(d + o, reinterpret_cast<const char*>(h->data()) + o, std::min(piece, bytes - o),
+                          hipMemcpyHostToDevice, st));
     return reinterpret_cast<const T*>(d);
   }
   void note(hipError_t e) {
@@ -397,6 +416,10 @@ struct RawBackend {
   void pair(PairTable& tb, const PArgs& a) {
     if (ok()) note(pair_launch(tb, a, st, [&](auto& v) { return upload(v); }));
   }
+  const double* consts(std::vector<double>& v) { return upload(v); }
+  void string(StringTable& tb, const StrArgs& a) {
+    if (ok()) note(string_launch(tb, a, st, [&](auto& v) { return upload(v); }));
+  }
 };
 
 // ------------------------------------------------------------------ driver
@@ -407,10 +430,17 @@ template <class BE>
 struct has_pair<BE, std::void_t<decltype(std::declval<BE&>().pair(std::declval<PairTable&>(), std::declval<const PArgs&>()))>>
     : std::true_type {};
 
+// whether a backend has the string chain launches
+template <class BE, class = void>
+struct has_string : std::false_type {};
+template <class BE>
+struct has_string<BE, std::void_t<decltype(std::declval<BE&>().string(std::declval<StringTable&>(), std::declval<const StrArgs&>()))>>
+    : std::true_type {};
+
 // close outputs one state can produce (sizes its slice of the result buffer)
 inline size_t max_outputs(int L, int p, int nrows, Want w) {
   return 1 + (w.env() ? size_t(L) * p : 0) + 2 * size_t(nrows) * L + (w.mom ? size_t(kEnergyOut) : 0) +
-         (w.pair ? pair_outputs(L, p) : 0);
+         (w.pair ? pair_outputs(L, p) : 0) + (w.str ? size_t(w.str->nops) : 0);
 }
 
 // Queue every launch of one chunk.  out_slot[i] is state i's index in the
@@ -441,6 +471,11 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
   if (want.pair) {
     if constexpr (has_pair<BE>::value)  // (a backend without the pair launch is never asked for pairs)
       pair_chunk(be, L, p, Q, S, *kets, out_slot, want.pair_occ, want.pair_hop, d_out, one, dests, tr);
+    return d_out;
+  }
+  if (want.str) {
+    if constexpr (has_string<BE>::value)  // (a backend without the string launches is never asked for strings)
+      string_chunk(be, L, p, Q, S, out_slot, *want.str, d_out, one, dests, tr);
     return d_out;
   }
   auto D = [&](int i, int b, int q) { return (q < 0 || q > Q) ? 0 : S[i]->dims[size_t(b) * Q1 + q]; };
@@ -846,7 +881,8 @@ double* run_chunk(BE& be, int L, int p, int Q, const std::vector<const StateDesc
 }
 
 // workspace bytes of every state alone (a chunk of several takes at most the
-// sum), by a dry run per distinct set of bond-sector dims (with kets: of every pair, per distinct dims of both)
+// sum), by a dry run per distinct set of bond-sector dims (with kets: of every pair, per distinct dims of both;
+// the operators of want.str, and so their supports, are those of the whole request)
 inline std::vector<size_t> workspace_needs(int L, int p, int Q, const std::vector<StateDesc>& desc,
                                            const std::vector<int>& rows, Want want, const Snap* snap = nullptr,
                                            const std::vector<StateDesc>* kets = nullptr) {
@@ -899,6 +935,9 @@ struct Outputs {
   double* povl = nullptr;
   double* pocc = nullptr;
   double* phop = nullptr;
+  // alone (ocg_observe_strings), complex: [nt][nops] <s|O_m|s> of the operators *str
+  const Strings* str = nullptr;
+  double* sout = nullptr;
 };
 
 // what the kernels must compute for the requested outputs (the diagonal of a
@@ -913,6 +952,7 @@ inline Want want_of(const Outputs& o) {
   w.pair_occ = o.pocc != nullptr;
   w.pair_hop = o.phop != nullptr && o.L > 1;
   w.pair = o.povl != nullptr || w.pair_occ || w.pair_hop;
+  w.str = o.sout ? o.str : nullptr;
   return w;
 }
 
@@ -941,6 +981,10 @@ inline void scatter(const std::vector<Dest>& dests, const double* res, const Out
           dst[2 * d.idx] = res[2 * j];
           dst[2 * d.idx + 1] = res[2 * j + 1];
         }
+        break;
+      case 9:
+        o.sout[2 * d.idx] = res[2 * j];
+        o.sout[2 * d.idx + 1] = res[2 * j + 1];
         break;
     }
   }

@@ -1863,7 +1863,12 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
   const int nst = int(desc.size());
   obs::Want want = obs::want_of(o);
   want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !sn) return 0;
+  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !want.str && !sn) return 0;
+  if (want.str) {
+    int wb = 0, wo = 0;
+    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
+    if (wo > obs::kStringMaxOrder) return fail(c, OCG_ECAP, "strings: a bond sector above order 512");
+  }
   if (sn) {
     int wb = 0, wo = 0;
     for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
@@ -1897,8 +1902,8 @@ static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, si
     int i1 = i0;
     size_t sum = 0;
     while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom || want.pair) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : want.pair ? "pairs" : "moments") +
+    if ((sn || want.mom || want.pair || want.str) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
+      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : want.pair ? "pairs" : want.str ? "strings" : "moments") +
                                      ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
                                      std::to_string(sum) + " B) exceeds the chunk budget");
     std::vector<const obs::StateDesc*> S, SY;
@@ -2318,6 +2323,51 @@ int ocg_observe_pairs_states(ocg_ctx* c, int n, const int* dims_x, const double*
   o.pocc = occ;
   o.phop = hop;
   return observe_staged(c, n, dims_x, x, o, nullptr, nullptr, "pairs", dims_y, y);
+}
+
+// the operators of a string request (f[nops][L][p][2], all finite) with their supports
+static int string_request(ocg_ctx* c, const double* f, int nops, obs::Strings& sr) {
+  if (nops < 0 || (nops > 0 && !f)) return fail(c, OCG_EINVAL, "bad operator tables");
+  const size_t nf = 2 * size_t(nops) * c->P.L * c->P.p;
+  for (size_t j = 0; j < nf; ++j)
+    if (!std::isfinite(f[j])) return fail(c, OCG_EINVAL, "a table entry is not finite");
+  sr.nops = nops;
+  sr.f = f;
+  sr.prepare(c->P.L, c->P.p);
+  return 0;
+}
+
+int ocg_observe_strings(ocg_ctx* c, int which, const int* ts, int nt, const double* f, int nops, double* out) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_strings(c->hbm, which, ts, nt, f, nops, out));
+  std::vector<int> slots;
+  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
+  obs::Strings sr;
+  if (int rc = string_request(c, f, nops, sr)) return rc;
+  if (nt == 0 || nops == 0) return 0;
+  if (!out) return fail(c, OCG_EINVAL, "bad output");
+  HIPCHK(c, hipSetDevice(c->device));
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.str = &sr;
+  o.sout = out;
+  return observe_slots(c, slots, 0, o, nullptr, nullptr);
+}
+
+int ocg_observe_strings_states(ocg_ctx* c, int n, const int* dims, const double* const* data, const double* f,
+                               int nops, double* out) {
+  if (!c) return OCG_EINVAL;
+  if (c->hbm) return hb(c, hbm_observe_strings_states(c->hbm, n, dims, data, f, nops, out));
+  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
+  obs::Strings sr;
+  if (int rc = string_request(c, f, nops, sr)) return rc;
+  if (n == 0 || nops == 0) return 0;
+  if (!out) return fail(c, OCG_EINVAL, "bad output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = staged_check(c, n, dims, -1)) return rc;
+  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
+  o.str = &sr;
+  o.sout = out;
+  return observe_staged(c, n, dims, data, o, nullptr, nullptr, "strings");
 }
 
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,

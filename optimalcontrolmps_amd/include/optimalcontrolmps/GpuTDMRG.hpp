@@ -399,6 +399,34 @@ class GpuTDMRG::Engine {
                   c, "ocg_observe_pairs");
     return o;
   }
+  // Expectations of products of diagonal one-site operators in the states ts (empty: all N) of a
+  // device-resident trajectory (ocg_observe_strings): tables[m] is L x p, row k - 1 the diagonal
+  // f[n] of operator m on site k (all 1: the site is outside its support).  Returns [e][m] =
+  // <s|O_m|s>, raw (not divided by the norm).
+  std::vector<std::vector<Cplx>> observeStrings(int which, const std::vector<int>& ts,
+                                                const std::vector<std::vector<Cplx>>& tables) {
+    std::vector<int> tt = ts;
+    if (ts.empty())
+      for (size_t t = 0; t < N; ++t) tt.push_back(int(t));
+    const size_t per = size_t(stepper.L) * stepper.p, nops = tables.size();
+    std::vector<Cplx> f;
+    for (const std::vector<Cplx>& t : tables) {
+      if (t.size() != per) throw std::invalid_argument("observeStrings: a table is not L x p");
+      f.insert(f.end(), t.begin(), t.end());
+    }
+    std::vector<Cplx> flat(tt.size() * nops, Cplx(0, 0));
+    ocg_ctx* c = shards[0].get();
+    detail::check(ocg_observe_strings(c, which, tt.data(), int(tt.size()), reinterpret_cast<const double*>(f.data()),
+                                      int(nops), reinterpret_cast<double*>(flat.data())),
+                  c, "ocg_observe_strings");
+    std::vector<std::vector<Cplx>> out(tt.size());
+    for (size_t e = 0; e < tt.size(); ++e) out[e].assign(flat.begin() + e * nops, flat.begin() + (e + 1) * nops);
+    return out;
+  }
+  // the chain length, the levels per site and the particle number of the trajectories
+  int sites() const { return stepper.L; }
+  int levels() const { return stepper.p; }
+  int particles() const { return tgt.Q; }
   // launches of one ocg_kernel_stats kind on shard 0 since the context was created (diagnostics: kind 0
   // counts the trajectory propagations)
   long kernelLaunches(int kind) {

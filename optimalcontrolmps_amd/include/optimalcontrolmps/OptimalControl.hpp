@@ -18,6 +18,8 @@
 //           getPsitFockProbability),
 //           observeMoments(which, ts) (optional: getPsitEnergies, with the stepper's hopping()),
 //           observePairs(which_x, tx, which_y, ty) (optional: getControlSensitivities),
+//           observeStrings(which, ts, tables), sites(), levels(), particles() (optional:
+//           getPsitStringExpectations, getPsitParityOrder, getPsitCountingStatistics),
 //           convertHessian(basis, Hu) (ControlBasis::convertHessian, src/ControlBasis.cpp:91-116).
 //
 // Host-side arithmetic kept verbatim from the reference: the regularisation
@@ -90,6 +92,57 @@ class OptimalControl {
     stdvec pr(amp.size());
     for (size_t e = 0; e < amp.size(); ++e) pr[e] = o.norm2[e] > 0 ? std::norm(amp[e]) / o.norm2[e] : 0.0;
     return pr;
+  }
+  // <psi_t|O_m|psi_t> for t in ts (empty: all) of products of diagonal one-site operators, [e][m], raw:
+  // tables[m] is L x p, row k - 1 the diagonal of operator m on site k (all 1: outside its support).
+  // Reads the device trajectory (Engine::observeStrings); nothing is propagated.  The host counterpart for
+  // one state is stringExpectation of correlations.hpp.  Only for steppers whose Engine has observeStrings().
+  std::vector<std::vector<Cplx>> getPsitStringExpectations(const std::vector<int>& ts,
+                                                           const std::vector<std::vector<Cplx>>& tables) const {
+    return engine->observeStrings(0, ts, tables);
+  }
+  // The parity (string) order of psi_t from site i: [e][j - 1] = <prod_{k=i..j} (-1)^(n_k - nbar)> / norm2
+  // for j >= i, entries below i are 0: the Mott insulator's order parameter as a quantum-gas microscope
+  // measures it.
+  rowmat getPsitParityOrder(const std::vector<int>& ts, int i, int nbar) const {
+    const int L = engine->sites(), p = engine->levels();
+    if (i < 1 || i > L) throw std::invalid_argument("getPsitParityOrder: site out of range");
+    std::vector<std::vector<Cplx>> tables(size_t(L - i + 2), std::vector<Cplx>(size_t(L) * p, Cplx(1, 0)));
+    for (int j = i; j <= L; ++j)
+      for (int k = i; k <= j; ++k)
+        for (int n = 0; n < p; ++n) tables[j - i][size_t(k - 1) * p + n] = ((n - nbar) % 2 == 0) ? 1.0 : -1.0;
+    const std::vector<std::vector<Cplx>> v = engine->observeStrings(0, ts, tables);  // (the last table: norm2)
+    rowmat out;
+    for (const std::vector<Cplx>& r : v) {
+      stdvec row(size_t(L), 0.0);
+      for (int j = i; j <= L; ++j) row[j - 1] = r[j - i].real() / r.back().real();
+      out.push_back(row);
+    }
+    return out;
+  }
+  // The counting statistics of the block of sites i..j in psi_t: [e][m] = P(N_A = m), m = 0..Q, from the
+  // Q + 1 generating-function values <exp(i theta_r N_A)>, theta_r = 2 pi r / (Q + 1), of the device and a
+  // discrete Fourier transform on the host (exact, since N_A <= Q).
+  rowmat getPsitCountingStatistics(const std::vector<int>& ts, int i, int j) const {
+    const int L = engine->sites(), p = engine->levels(), Q1 = engine->particles() + 1;
+    if (i < 1 || j < i || j > L) throw std::invalid_argument("getPsitCountingStatistics: block out of range");
+    const double two_pi = 2 * std::acos(-1.0);
+    std::vector<std::vector<Cplx>> tables(size_t(Q1), std::vector<Cplx>(size_t(L) * p, Cplx(1, 0)));
+    for (int r = 0; r < Q1; ++r)
+      for (int k = i; k <= j; ++k)
+        for (int n = 0; n < p; ++n) tables[r][size_t(k - 1) * p + n] = std::polar(1.0, two_pi * r * n / Q1);
+    const std::vector<std::vector<Cplx>> G = engine->observeStrings(0, ts, tables);  // (r = 0: norm2)
+    rowmat out;
+    for (const std::vector<Cplx>& g : G) {
+      stdvec row(size_t(Q1), 0.0);
+      for (int m = 0; m < Q1; ++m) {
+        Cplx s = 0;
+        for (int r = 0; r < Q1; ++r) s += std::polar(1.0, -two_pi * r * m / Q1) * g[r];
+        row[m] = s.real() / Q1 / g[0].real();
+      }
+      out.push_back(row);
+    }
+    return out;
   }
   // E_t = <psi_t|H(u_t)|psi_t> / <psi_t|psi_t> and Var_t = <H(u_t)^2> - E_t^2 of the stored
   // psi_t with u = the control as given to the last propagation (GROUP coefficients are

@@ -11,6 +11,10 @@
 //   entanglementEntropy(sites, psi)                von Neumann entropy of every bond,
 //                                                  weights below 1e-12 dropped (:120-149)
 //
+//   stringExpectation(psi, tables)                 <psi| prod_k F_{m,k} |psi> for diagonal one-site
+//                                                  operators (no counterpart in the reference): the
+//                                                  host route of ocg_observe_strings
+//
 // Site operators as include/BH_sites.h:114-176 defines them: "N", "A", "Adag",
 // "N(N-1)", "NN" and "Id" (which, like the reference's, has no n = 0 entry).
 //
@@ -376,6 +380,67 @@ inline double correlationTerm(const BoseHubbard& sites, const MPS& psi, const st
     for (int j = 0; j < N; ++j) A[size_t(i) * N + j] = rho[i][j];
   const std::vector<double> w = obs::heev(A, N);
   return *std::max_element(w.begin(), w.end());
+}
+
+namespace obs {
+// leftStep for a complex diagonal operator: E'[c'][c] = sum conj(A[a'][n][c']) f[n] E[a'][a] A[a][n][c]
+inline cmat leftStepDiag(const Dense& D, int k, const cmat& E, const Cplx* f) {
+  const int cl = D.chi[k - 1], cr = D.chi[k], p = D.p;
+  const cmat& A = D.A[k];
+  cmat T(size_t(cl) * p * cr, Cplx(0, 0));  // T[a'][n][c] = f[n] sum_a E[a'][a] A[a][n][c]
+  for (int x = 0; x < cl; ++x)
+    for (int a = 0; a < cl; ++a) {
+      const Cplx e = E[size_t(x) * cl + a];
+      if (e == Cplx(0, 0)) continue;
+      for (int n = 0; n < p; ++n) {
+        const Cplx w = e * f[n];
+        const Cplx* src = &A[(size_t(a) * p + n) * cr];
+        Cplx* dst = &T[(size_t(x) * p + n) * cr];
+        for (int c = 0; c < cr; ++c) dst[c] += w * src[c];
+      }
+    }
+  cmat R(size_t(cr) * cr, Cplx(0, 0));
+  for (size_t xn = 0; xn < size_t(cl) * p; ++xn) {
+    const Cplx* ab = &A[xn * cr];
+    const Cplx* t = &T[xn * cr];
+    for (int cp = 0; cp < cr; ++cp) {
+      const Cplx b = std::conj(ab[cp]);
+      if (b == Cplx(0, 0)) continue;
+      Cplx* dst = &R[size_t(cp) * cr];
+      for (int c = 0; c < cr; ++c) dst[c] += b * t[c];
+    }
+  }
+  return R;
+}
+}  // namespace obs
+
+// <psi|O_m|psi> (raw, not divided by the norm) of the operators O_m = prod_k F_{m,k},
+// F_{m,k} = sum_n tables[m][(k - 1) p + n] P_k(n): every table is L x p, a row of ones leaves the site
+// outside the operator's support, and the sweep runs over the support alone (an empty support gives the
+// norm).  What OptimalControl::getPsitStringExpectations takes from the device for the stored trajectory.
+inline std::vector<Cplx> stringExpectation(const MPS& psi, const std::vector<std::vector<Cplx>>& tables) {
+  const obs::Dense D = obs::dense(psi);
+  const obs::Envs V = obs::envs(D);
+  const int L = psi.L, p = psi.p;
+  std::vector<Cplx> out;
+  for (const std::vector<Cplx>& f : tables) {
+    if (f.size() != size_t(L) * p) throw std::invalid_argument("stringExpectation: a table is not L x p");
+    int a = 0, b = 0;
+    for (int k = 1; k <= L; ++k)
+      for (int n = 0; n < p; ++n)
+        if (f[size_t(k - 1) * p + n] != Cplx(1, 0)) {
+          if (!a) a = k;
+          b = k;
+        }
+    if (!a) {
+      out.push_back(obs::closeEnv(V.Lenv[L], V.Renv[L]));
+      continue;
+    }
+    obs::cmat E = V.Lenv[a - 1];
+    for (int k = a; k <= b; ++k) E = obs::leftStepDiag(D, k, E, &f[size_t(k - 1) * p]);
+    out.push_back(obs::closeEnv(E, V.Renv[b]));
+  }
+  return out;
 }
 
 // <H(J, U)> and <H^2> - <H>^2 of entry e of device moments (Engine::observeMoments)

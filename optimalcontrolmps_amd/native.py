@@ -45,9 +45,11 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
     deps = {
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
                   "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
-                  "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp"],
+                  "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp",
+                  "observe_string.hpp"],
         "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
-                "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp"],
+                "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp",
+                "observe_string.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
@@ -140,6 +142,8 @@ SIGNATURES = [
     ("ocg_observe_moments_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), dp]),
     ("ocg_observe_pairs", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, ip, C.c_int, dp, dp, dp]),
     ("ocg_observe_pairs_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), ip, C.POINTER(dp), dp, dp, dp]),
+    ("ocg_observe_strings", C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, dp, C.c_int, dp]),
+    ("ocg_observe_strings_states", C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(dp), dp, C.c_int, dp]),
     ("ocg_convert_hessian", C.c_int, [C.c_void_p, dp, C.c_int, dp, C.c_int, dp]),
     ("ocg_denmat_decomp", C.c_int, [C.c_void_p, C.c_int, ip, ip, C.POINTER(dp), C.c_double, C.c_int, ip,
                                     C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
@@ -707,6 +711,74 @@ class Engine:
         self._chk(lib().ocg_observe_pairs_states(self.h, n, dx.ctypes.data_as(ip), datx, dy.ctypes.data_as(ip), daty,
                                                  *ptrs), "ocg_observe_pairs_states")
         return out
+
+    def _string_tables(self, f):
+        f = np.ascontiguousarray(np.asarray(f, np.complex128))
+        if f.ndim != 3 or f.shape[1:] != (self.L, self.p):
+            raise ValueError(f"operator tables must have shape (nops, {self.L}, {self.p})")
+        return f
+
+    def observe_strings(self, which, ts, f):
+        """Expectations of products of diagonal one-site operators in the device trajectory states
+        (ocg_observe_strings): which / ts as observe(); f complex (nops, L, p), operator m is the product
+        over the sites k of sum_n f[m][k-1][n] P_k(n) (a site whose table is all 1 is outside the
+        operator's support).  Returns complex (nt, nops) = <s|O_m|s>, raw (not divided by norm2)."""
+        tt, pt = _i(list(range(self.N)) if ts is None else list(ts))
+        f = self._string_tables(f)
+        out = np.zeros((len(tt), len(f)), np.complex128)
+        self._chk(lib().ocg_observe_strings(self.h, int(which), pt, len(tt), f.ctypes.data_as(dp), len(f),
+                                            out.ctypes.data_as(dp)), "ocg_observe_strings")
+        return out
+
+    def observe_strings_states(self, states, f):
+        """observe_strings() for caller-supplied host states of any gauge or norm
+        (ocg_observe_strings_states)."""
+        n = len(states)
+        f = self._string_tables(f)
+        out = np.zeros((n, len(f)), np.complex128)
+        if n == 0:
+            return out
+        dims, raws, data = self._staged(states)
+        self._chk(lib().ocg_observe_strings_states(self.h, n, dims.ctypes.data_as(ip), data, f.ctypes.data_as(dp),
+                                                   len(f), out.ctypes.data_as(dp)), "ocg_observe_strings_states")
+        return out
+
+    def _norm2_of_strings(self, which, ts, f):
+        """observe_strings() with the identity appended: (values, norm2)"""
+        f = np.concatenate([f, np.ones((1, self.L, self.p), np.complex128)])
+        out = self.observe_strings(which, ts, f)
+        return out[:, :-1], out[:, -1].real
+
+    def parity_order(self, which, ts, i, nbar):
+        """The parity (string) order from site i (1-based): real (nt, L), entry j-1 =
+        <prod_{k=i..j} (-1)^(n_k - nbar)> / norm2 for j >= i, entries below i are 0."""
+        i = int(i)
+        if not 1 <= i <= self.L:
+            raise ValueError("site out of 1..L")
+        sign = np.array([(-1.0) ** (n - int(nbar)) for n in range(self.p)])
+        f = np.ones((self.L - i + 1, self.L, self.p), np.complex128)
+        for m in range(len(f)):
+            f[m, i - 1:i + m] = sign
+        val, norm2 = self._norm2_of_strings(which, ts, f)
+        out = np.zeros((len(val), self.L))
+        out[:, i - 1:] = val.real / norm2[:, None]
+        return out
+
+    def counting_statistics(self, which, ts, i, j):
+        """The distribution of the boson number in the sites i..j (1-based, inclusive): real (nt, Q+1),
+        entry m = P(N_A = m).  The Q+1 generating-function values G_r = <exp(i theta_r N_A)>,
+        theta_r = 2 pi r / (Q+1), come from the device; P(m) = Re[sum_r exp(-i theta_r m) G_r / (Q+1)] / norm2
+        (exact, since N_A <= Q) is formed on the host."""
+        i, j = int(i), int(j)
+        if not 1 <= i <= j <= self.L:
+            raise ValueError("block out of 1 <= i <= j <= L")
+        Q1 = self.Q + 1
+        theta = 2 * np.pi * np.arange(Q1) / Q1
+        f = np.ones((Q1, self.L, self.p), np.complex128)
+        f[:, i - 1:j, :] = np.exp(1j * theta[:, None, None] * np.arange(self.p)[None, None, :])
+        G, norm2 = self._norm2_of_strings(which, ts, f)
+        dft = np.exp(-1j * np.outer(theta, np.arange(Q1)))  # [r][m]
+        return (G @ dft).real / Q1 / norm2[:, None]
 
     def stats(self, kind):
         ms = C.c_double(); n = C.c_long(); b = C.c_double(); f = C.c_double(); s = C.c_long()

@@ -2,7 +2,7 @@
 was before: one ocg_get_state copy per state (a lower bound of that path, which
 adds the host contraction of correlations.hpp on top).
 
-    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|e1|e4|pairs|all] [--reps R] [--out DIR]
+    python -m optimalcontrolmps_amd.tools.observe_timing [--config 1|4|s1|s4|p1|p4|e1|e4|pairs|strings|all] [--reps R] [--out DIR]
 
 One process; every shape is warmed up; each timed call ends in a device
 synchronise (both entry points return only after their results are on the
@@ -38,6 +38,13 @@ N_t = 201: the chain kernel, the forced task-list path (OCG_OBS_PAIR_CHAIN=0) an
 the host route (ocg_get_state of both trajectories plus the numpy block
 contraction of tests/pair_reference.py), alternating.  Writes
 observe_pairs_config1.json.
+
+strings: the string-operator expectations (ocg_observe_strings) of every psi_t at config 1,
+N_t = 201, for two operator sets, the parity-order row from site 1 (L operators) and the
+counting statistics of the sites 2..4 (Q + 1 operators): the chain kernels, the forced
+task-list path (OCG_OBS_STRING_CHAIN=0) and the host route (ocg_get_state plus the numpy
+block contraction of tests/string_reference.py), alternating, and each device route
+back to back.  Writes observe_strings_config1.json.
 """
 from __future__ import annotations
 
@@ -414,9 +421,73 @@ def pairs1(reps):
     return res
 
 
+def strings1(reps):
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import string_reference as T
+    L, p, Q, J, dt, cut, maxm, Nt = 5, 5, 5, 1.0, 0.01, 1e-8, 80, 201
+    z = np.load(os.path.join(GOLDEN, "states.npz"), allow_pickle=False)
+    ini = MPS(L, p, Q, z["L5_p5_N5_J1_U2.5/dims"], z["L5_p5_N5_J1_U2.5/data"])
+    tgt = MPS(L, p, Q, z["L5_p5_N5_J1_U50/dims"], z["L5_p5_N5_J1_U50/data"])
+    eng = Engine(L, p, Q, J, dt, cut, maxm)
+    eng.set_states(tgt, ini)
+    eng.propagate(np.linspace(2.5, 50.0, Nt), 1)
+    sets = {"parity": T.parity_tables(L, p, 1, 1), "counting": T.counting_tables(L, p, Q, 2, 4)}
+    res = {"config": "1: L=5 p=5 Q=5 chi<=80 N_t=201, LDS engine, every psi_t",
+           "sector_max": int(max(eng.state(0, t).dims.max() for t in (0, Nt // 2, Nt - 1))),
+           "operators": {k: len(f) for k, f in sets.items()}}
+    norm2 = eng.observe(0, None, outputs=("norm2",))["norm2"]
+    for name, f in sets.items():
+        def forced_lists():
+            os.environ["OCG_OBS_STRING_CHAIN"] = "0"
+            try:
+                return eng.observe_strings(0, None, f)
+            finally:
+                del os.environ["OCG_OBS_STRING_CHAIN"]
+
+        def host_route():
+            out = []
+            for t in range(Nt):
+                x = eng.state(0, t)
+                out.append(T.strings_ref(x.dims, x.data, L, p, Q, f))
+            return np.array(out)
+        cases = {"chain": lambda: eng.observe_strings(0, None, f), "lists": forced_lists}
+        for c in cases.values():
+            c()
+            c()
+        host_route()
+        t = {k: [] for k in cases}
+        t["host_get_state_plus_numpy"] = []
+        for i in range(reps):  # alternating; the host route joins every eighth round
+            for k, c in cases.items():
+                t[k].append(timed(c))
+            if i % 8 == 0:
+                t["host_get_state_plus_numpy"].append(timed(host_route))
+        r = {k: spread(v) for k, v in t.items()}
+        # each device route on its own as well: a call's host-side cost can surface in the call after it
+        for k, c in cases.items():
+            r[k + "_back_to_back"] = spread([timed(c) for _ in range(max(8, reps // 2))][2:])
+        for k in cases:
+            eng.reset_stats()
+            cases[k]()
+            r[k + "_kind9"] = eng.stats(9)
+            r[k + "_vs_host"] = r["host_get_state_plus_numpy"]["median_ms"] / r[k]["median_ms"]
+        r["chain_vs_lists"] = r["lists"]["median_ms"] / r["chain"]["median_ms"]
+        a, b, h = cases["chain"](), forced_lists(), host_route()
+        sc = T.scale(norm2[:, None], f[None])
+        r["chain_lists_max_dev_per_state"] = float((np.abs(a - b) / sc).max())
+        r["chain_host_max_dev_per_state"] = float((np.abs(a - h) / sc).max())
+        res[name] = r
+    par = eng.parity_order(0, [0, Nt - 1], 1, 1)
+    res["parity_order_first_last"] = [par[0].tolist(), par[1].tolist()]
+    res["counting_2_4_last"] = eng.counting_statistics(0, [Nt - 1], 2, 4)[0].tolist()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "e1", "e4", "pairs", "all"])
+    ap.add_argument("--config", default="all", choices=["1", "4", "s1", "s4", "p1", "p4", "e1", "e4", "pairs", "strings",
+                                                       "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
@@ -425,13 +496,13 @@ def main():
                            ("s1", spectrum1, a.reps), ("s4", spectrum4, max(3, a.reps // 4)),
                            ("p1", sample1, a.reps), ("p4", sample4, max(3, a.reps // 4)),
                            ("e1", energy1, a.reps), ("e4", energy4, max(3, a.reps // 4)),
-                           ("pairs", pairs1, a.reps)):
+                           ("pairs", pairs1, a.reps), ("strings", strings1, a.reps)):
         if a.config in (name, "all"):
             res = fn(reps)
             res["command"] = f"python -m optimalcontrolmps_amd.tools.observe_timing --config {name} --reps {a.reps}"
             kind = {"s": "observe_spectrum_config", "p": "observe_sample_config",
                     "e": "observe_energy_config"}.get(name[0], "observe_config")
-            out = "observe_pairs_config1.json" if name == "pairs" else f"{kind}{name[-1]}.json"
+            out = f"observe_{name}_config1.json" if name in ("pairs", "strings") else f"{kind}{name[-1]}.json"
             with open(os.path.join(a.out, out), "w") as f:
                 json.dump(res, f, indent=1)
             print(json.dumps(res))
