@@ -142,6 +142,32 @@ void* emu_new_ex(int L, int p, int Q, double J, double dt, double cutoff, int ma
   }
   return e;
 }
+// build_fast_plan's verdict on a shape and the sizes of its plan (tests/golden/fast_plan_census.json):
+// 1 accepted, 0 rejected (why receives why_not), -1 no parameter block for the shape.  out[10]: np, step
+// operations, the maxima over the operations of nth, T, ngrp, maxr, dot, nf, ns, and whether the padded
+// overlap's plan builds and fits the general chain's region (emu_new_ex's condition)
+int emu_fast_census(int L, int p, int Q, char* why, int nwhy, int* out) {
+  using namespace ocg::fastp;
+  auto* e = static_cast<Emu*>(emu_new(L, p, Q, 1.0, 0.01, 1e-8, 5000));
+  if (nwhy > 0) why[0] = 0;
+  for (int i = 0; i < 10; ++i) out[i] = 0;
+  if (!e) return -1;
+  const ocg_host::FastPlanBuild fb = ocg_host::build_fast_plan(e->P, e->md);
+  if (nwhy > 0) std::snprintf(why, size_t(nwhy), "%s", fb.why_not.c_str());
+  const bool ok = fb.why_not.empty();
+  if (ok) {
+    const std::vector<int>& I = fb.plan;
+    out[0] = I[kHNp];
+    out[1] = I[kHNops];
+    const int f[7] = {kOhNth, kOhT, kOhNgrp, kOhMaxr, kOhDot, kOhNf, kOhNs};
+    for (int o = 0; o < I[kHNops]; ++o)
+      for (int i = 0; i < 7; ++i) out[2 + i] = std::max(out[2 + i], I[I[kHOps + o] + f[i]]);
+    const std::vector<int> ov = ocg_host::build_overlap_plan(e->P, e->md);
+    out[9] = !ov.empty() && ocg_host::overlap_lds_bytes(ov, e->P) <= ((e->lds + 255) & ~255);
+  }
+  delete e;
+  return ok ? 1 : 0;
+}
 void emu_free(void* h) { delete static_cast<Emu*>(h); }
 int emu_lds_bytes(void* h) { return static_cast<Emu*>(h)->lds; }
 

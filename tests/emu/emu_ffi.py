@@ -29,6 +29,24 @@ def lib():
     return _lib
 
 
+CENSUS_FIELDS = ("np", "nops", "nth", "T", "ngrp", "maxr", "dot", "nf", "ns", "ovl")
+
+
+def fast_census(L, p, Q):
+    """build_fast_plan's verdict on (L, p, Q): (accepted, why_not, sizes), sizes a dict of
+    CENSUS_FIELDS (np, the step operations, the maxima over the operations of nth .. ns, and
+    whether the padded overlap's plan is in use) for an accepted shape, else None"""
+    fn = lib().emu_fast_census
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, ip]
+    why = C.create_string_buffer(256)
+    out = np.zeros(len(CENSUS_FIELDS), np.int32)
+    rc = fn(L, p, Q, why, len(why), out.ctypes.data_as(ip))
+    if rc < 0:
+        raise RuntimeError("no parameter block for this shape")
+    return bool(rc), why.value.decode(), ({k: int(v) for k, v in zip(CENSUS_FIELDS, out)} if rc else None)
+
+
 class Emu:
     def __init__(self, L, p, Q, J, dt, cutoff, maxm, fast):
         self.L, self.p, self.Q = L, p, Q
