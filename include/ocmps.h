@@ -96,7 +96,12 @@ size_t ocg_mps_nelem(int L, int p, int Q, const int* dims);
 
 /* ------------------------------------------ TimeStepper-level operations
  * Host MPS in, host MPS out (compact format above).  out_cap is the capacity
- * of out_data in complex elements; *out_nelem receives the size written. */
+ * of out_data in complex elements; *out_nelem receives the size written.
+ * Input dims are checked on the host before anything reaches the device, on
+ * both engines (these calls, ocg_step_batch, ocg_overlap, ocg_apply_dH,
+ * ocg_set_states): a negative entry, or a bond 0 / bond L that is not the one
+ * state q = 0 / q = Q, OCG_EINVAL; a sector above its Schmidt-rank bound
+ * min(HS_left, HS_right) OCG_ECAP. */
 
 /* BH_tDMRG::step(psi, from, to, propagateForward) (src/BH_tDMRG.cpp:111-230) */
 int ocg_step(ocg_ctx* ctx, const int* dims, const double* data, double from, double to, int forward,

@@ -2306,6 +2306,28 @@ int widest_of(const hbm::Engine& E, const int* dims) {
   }
   return w;
 }
+// The dims of a state a chain is loaded from (stepped, overlapped, zipped up with dH, or kept as target /
+// initial state), checked before anything is reserved or uploaded: what the LDS engine's validate_dims
+// rejects.  A sector above its Schmidt-rank bound md would overrun the per-site buffer of a chain while the
+// state's total still fits its slot.  (The staged observable calls take over-parametrised states and keep
+// staged_check.)
+void check_dims(const hbm_engine* h, const int* dims) {
+  const hbm::Engine& E = *h->E;
+  if (!dims) throw hbm::Error(1, "null dims");
+  for (int q = 0; q < E.Q1; ++q)
+    if (dims[q] != (q == 0 ? 1 : 0)) throw hbm::Error(1, "bond 0 must be one state with q = 0");
+  for (int q = 0; q < E.Q1; ++q)
+    if (dims[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
+      throw hbm::Error(1, "bond L must be one state with q = Q (particle number mismatch?)");
+  for (int b = 0; b <= E.L; ++b)
+    for (int q = 0; q < E.Q1; ++q) {
+      const int v = dims[b * E.Q1 + q];
+      if (v < 0) throw hbm::Error(1, "negative bond dimension");
+      if (v > h->md[size_t(b) * E.Q1 + q])
+        throw hbm::Error(2, "bond " + std::to_string(b) + " sector " + std::to_string(q) +
+                                " exceeds its Schmidt-rank bound");
+    }
+}
 // Every entry point runs inside guard(): exceptions become status codes, and a
 // failed call leaves no chain acquired (work already queued on the stream is
 // drained first, so a later call cannot reuse a buffer a kernel still writes).
@@ -2643,6 +2665,7 @@ int hbm_steps(hbm_engine* h, int n, const int* dims, const double* const* data, 
   return guard(h, [&] {
     hbm::Engine& E = *h->E;
     const int nsq = (E.L + 1) * E.Q1;
+    for (int i = 0; i < n; ++i) check_dims(h, dims + size_t(i) * nsq);
     for (int i = 0; i < n; ++i) E.set_caps(widest_of(E, dims + size_t(i) * nsq));
     E.reserve_states(size_t(h->xih_base() + h->N + n));
     const int sb = h->xih_base() + h->N;
@@ -2673,6 +2696,8 @@ int hbm_overlap(hbm_engine* h, const int* dx, const double* x, const int* dy, co
                 double* out) {
   return guard(h, [&] {
     hbm::Engine& E = *h->E;
+    check_dims(h, dx);
+    check_dims(h, dy);
     E.set_caps(std::max(widest_of(E, dx), widest_of(E, dy)));
     E.reserve_states(size_t(h->traj_slots(h->N)));
     const int sb = h->xih_base() + h->N;
@@ -2690,6 +2715,7 @@ int hbm_apply_dH(hbm_engine* h, const int* dims, const double* data, int* out_di
                  size_t* nelem, double* norm) {
   return guard(h, [&] {
     hbm::Engine& E = *h->E;
+    check_dims(h, dims);
     E.set_caps(widest_of(E, dims));
     E.reserve_states(size_t(h->xih_base() + h->N + 1));
     const int sb = h->xih_base() + h->N;
@@ -2711,6 +2737,8 @@ int hbm_apply_dH(hbm_engine* h, const int* dims, const double* data, int* out_di
 int hbm_set_states(hbm_engine* h, const int* dt_, const double* t, const int* di, const double* in) {
   return guard(h, [&] {
     hbm::Engine& E = *h->E;
+    check_dims(h, dt_);
+    check_dims(h, di);
     int wid = 0;
     for (int b = 0; b <= E.L; ++b) {
       int a = 0, c = 0;
@@ -3833,6 +3861,7 @@ int hbm_ground_state(hbm_engine* h, const int* dims, const double* data, double 
   int done = 0;
   const int rc = guard(h, [&] {
     hbm::Engine& E = *h->E;
+    check_dims(h, dims);
     E.set_caps(widest_of(E, dims));
     E.reserve_states(size_t(h->traj_slots(h->N)));
     const int prev = h->xih_base() + h->N;  // scratch slot after the trajectories
