@@ -37,14 +37,12 @@
 #include "hbm.hpp"
 #include "hbm_device.hpp"
 #include "observe.hpp"
+#include "observe_front.hpp"
 
 namespace hbm {
 
 // ---------------------------------------------------------------- errors
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
+using Error = obs::Error;  // an OCG_E* status and its message
 #define HCK(expr)                                                                                 \
   do {                                                                                            \
     hipError_t e_ = (expr);                                                                       \
@@ -3264,123 +3262,6 @@ obs::StateDesc obs_desc(const hbm::Engine& E, const State& s) {
   return d;
 }
 
-// the observables of state slots[i] into entry out0 + i of the outputs, in
-// chunks whose workspace fits half the free HBM
-void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr,
-                   const std::vector<obs::StateDesc>* kets = nullptr);
-// with so the spectrum stages run too and their results go to *so; with sn the snapshot
-// launch follows the right sweep instead and its results go to sn's outputs
-void observe_slots(hbm_engine* h, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                   double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
-  hbm::Engine& E = *h->E;
-  const int L = E.L, nst = int(slots.size());
-  std::vector<obs::StateDesc> desc(nst);
-  for (int i = 0; i < nst; ++i) {
-    desc[i] = obs_desc(E, E.states[slots[i]]);
-    if (bond)
-      for (int b = 0; b <= L; ++b) bond[(out0 + i) * (L + 1) + b] = E.states[slots[i]].dims.bond(b);
-  }
-  observe_descs(h, desc, out0, o, occ_buf, so, sn);
-}
-
-// the chunks of observe.hpp's driver over states described on the device (with kets: over the pairs
-// bra desc[i], ket (*kets)[i])
-void observe_descs(hbm_engine* h, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                   double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn,
-                   const std::vector<obs::StateDesc>* kets) {
-  hbm::Engine& E = *h->E;
-  const int L = E.L, nst = int(desc.size());
-  obs::Want want = obs::want_of(o);
-  want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !want.str && !sn) return;
-  if (want.str) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
-    if (wo > obs::kStringMaxOrder) throw hbm::Error(2, "strings: a bond sector above order 512");
-  }
-  if (sn) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
-    if (wo > obs::kSampleMaxOrder) throw hbm::Error(2, "snapshots: a bond sector above order 512");
-  }
-  if (want.pair) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) {
-      obs::widest(desc[i], L, E.Q1, wb, wo);
-      obs::widest((*kets)[i], L, E.Q1, wb, wo);
-    }
-    if (wo > obs::kPairMaxOrder) throw hbm::Error(2, "pairs: a bond sector above order 512");
-  }
-  if (want.mom) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
-    if (wo > obs::kEnergyMaxOrder) throw hbm::Error(2, "moments: a bond sector above order 512");
-  }
-  if (so) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], L, E.Q1, wb, wo);
-    if (so->weights() && so->wcap < wb)
-      throw hbm::Error(2, "wcap " + std::to_string(so->wcap) + " below the largest bond dimension " +
-                              std::to_string(wb));
-    if (wo > obs::kEigMaxOrder) throw hbm::Error(2, "spectrum: a bond sector above order 512");
-  }
-  const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(L, E.p, E.Q, desc, rows, want, sn, kets);
-  const size_t budget = obs::chunk_budget();
-  for (int i0 = 0; i0 < nst;) {
-    int i1 = i0;
-    size_t sum = 0;
-    while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom || want.pair || want.str) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      throw hbm::Error(6, std::string(sn ? "snapshots" : want.pair ? "pairs" : want.str ? "strings" : "moments") +
-                              ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
-                              std::to_string(sum) + " B) exceeds the chunk budget");
-    std::vector<const obs::StateDesc*> S, SY;
-    std::vector<size_t> os;
-    for (int i = i0; i < i1; ++i) {
-      S.push_back(&desc[i]);
-      if (kets) SY.push_back(&(*kets)[i]);
-      os.push_back(out0 + i);
-    }
-    ObsBackend be{E};
-    std::vector<obs::Dest> dests;
-    Timer t(h, 9);
-    obs::Spec sp;
-    const double* d_out =
-        obs::run_chunk(be, L, E.p, E.Q, S, os, rows, want, dests, h->obs_tr, so ? &sp : nullptr, sn,
-                       kets ? &SY : nullptr);
-    if (sn) HCK(sn->fetch(out0 + i0, S.size(), L, E.st));
-    std::vector<double> res(2 * std::max<size_t>(dests.size(), 1));
-    if (!dests.empty())
-      HCK(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost, E.st));
-    std::vector<double> ent, wts;
-    std::vector<int> status;
-    if (so) {  // only results leave the device: the weights when they are asked for
-      ent.resize(std::max<size_t>(S.size() * (L - 1), 1));
-      status.resize(std::max<size_t>(sp.nstatus, 1));
-      wts.resize(so->weights() ? std::max<size_t>(sp.nw, 1) : 0);
-      if (L > 1)
-        HCK(hipMemcpyAsync(ent.data(), sp.d_ent, sizeof(double) * S.size() * (L - 1), hipMemcpyDeviceToHost, E.st));
-      if (sp.nstatus)
-        HCK(hipMemcpyAsync(status.data(), sp.d_status, sizeof(int) * sp.nstatus, hipMemcpyDeviceToHost, E.st));
-      if (so->weights() && sp.nw)
-        HCK(hipMemcpyAsync(wts.data(), sp.d_w, sizeof(double) * sp.nw, hipMemcpyDeviceToHost, E.st));
-    }
-    t.stop();
-    E.sync();
-    if (so) {
-      for (size_t j = 0; j < sp.nstatus; ++j)
-        if (status[j]) throw hbm::Error(5, "spectrum: a Jacobi eigen block did not converge");
-      obs::scatter_spectrum(sp, S, os, L, E.Q1, ent.data(), wts.data(), *so);
-    }
-    obs::scatter(dests, res.data(), o, occ_buf);
-    if (o.nrows > 0 && (o.ada || o.nn))
-      for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
-    i0 = i1;
-  }
-}
-
 // caller-supplied states staged per batch: a quarter of the free HBM, 64 at the most
 int hbm_batch_states(hbm_engine* h) {
   size_t fr = 0, tot = 0;
@@ -3389,127 +3270,83 @@ int hbm_batch_states(hbm_engine* h) {
   return int(std::max(1.0, std::min(64.0, 0.25 * double(fr) / per)));
 }
 
-void observe_check_rows(const hbm::Engine& E, const int* rows, int nrows) {
-  if (nrows < 0 || (nrows > 0 && !rows)) throw hbm::Error(1, "bad rows");
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 1 || rows[i] > E.L) throw hbm::Error(1, "row (start site) out of 1..L");
-}
-
-// the dims of caller-supplied states, before anything is written (wcap >= 0: the
-// bond dimensions must fit it)
-void staged_check(const hbm::Engine& E, int n, const int* dims, int wcap) {
-  const int nsq = (E.L + 1) * E.Q1;
-  for (int i = 0; i < n; ++i) {
-    const int* d = dims + size_t(i) * nsq;
-    for (int j = 0; j < nsq; ++j)
-      if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
-    for (int q = 0; q < E.Q1; ++q)
-      if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
-        throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
-    for (int b = 1; b < E.L && wcap >= 0; ++b) {
-      long sum = 0;
-      for (int q = 0; q < E.Q1; ++q) sum += d[size_t(b) * E.Q1 + q];
-      if (sum > wcap) throw hbm::Error(2, "wcap below the largest bond dimension of the states");
+// this engine as observe_front.hpp sees it
+struct HbmFront {
+  hbm_engine* h;
+  hbm::Engine& E;
+  const int L, p, Q;
+  explicit HbmFront(hbm_engine* h_) : h(h_), E(*h_->E), L(E.L), p(E.p), Q(E.Q) {}
+  int N() const { return h->N; }
+  hipStream_t stream() const { return E.st; }
+  bool have(int which) const { return which == 0 ? h->have_psi : which == 1 ? h->have_xi : h->have_xih; }
+  int base(int which) const { return which == 0 ? h->psi_base() : which == 1 ? h->xi_base() : h->xih_base(); }
+  void describe(const std::vector<int>& slots, size_t out0, int* bond, std::vector<obs::StateDesc>& desc) {
+    desc.resize(slots.size());
+    for (size_t i = 0; i < slots.size(); ++i) {
+      desc[i] = obs_desc(E, E.states[slots[i]]);
+      if (bond)
+        for (int b = 0; b <= L; ++b) bond[(out0 + i) * (L + 1) + b] = E.states[slots[i]].dims.bond(b);
     }
   }
-}
-
-// Caller-supplied states staged a batch at a time in the compact interchange format
-// itself: its blocks are the contiguous row-major matrices the descriptors want, and a
-// sector may be larger than the Hilbert-space bound of the state slots (a padded or
-// over-parametrised state).
-// With dims_y / data_y the states are the bras of pairs and those the kets, staged behind them.
-void observe_staged(hbm_engine* h, int n, const int* dims, const double* const* data, const obs::Outputs& o,
-                    const obs::SpecOutputs* so, obs::Snap* sn, const int* dims_y = nullptr,
-                    const double* const* data_y = nullptr) {
-  hbm::Engine& E = *h->E;
-  const int nsq = (E.L + 1) * E.Q1;
-  const int B = std::min(n, 64);
-  for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb0 = std::min(B, n - i0), nb = dims_y ? 2 * nb0 : nb0;
-    // entry i of the batch: state i0 + i, or for i >= nb0 the ket i0 + i - nb0
-    auto dims_of = [&](int i) { return i < nb0 ? dims + size_t(i0 + i) * nsq : dims_y + size_t(i0 + i - nb0) * nsq; };
-    auto data_of = [&](int i) { return i < nb0 ? data[i0 + i] : data_y[i0 + i - nb0]; };
-    std::vector<size_t> at(nb + 1, 0);
-    for (int i = 0; i < nb; ++i) {
-      obs::StateDesc tmp;
-      at[i + 1] = at[i] + obs::compact_desc(E.L, E.p, E.Q, dims_of(i), nullptr, tmp);
-    }
-    hbm::DBuf<double> stage;
-    stage.reserve(2 * std::max<size_t>(at[nb], 1));
-    std::vector<obs::StateDesc> desc(nb);
-    for (int i = 0; i < nb; ++i) {
-      if (at[i + 1] > at[i])
-        HCK(hipMemcpyAsync(stage.p + 2 * at[i], data_of(i), 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice,
-                           E.st));
-      obs::compact_desc(E.L, E.p, E.Q, dims_of(i), stage.p + 2 * at[i], desc[i]);
-    }
-    std::vector<obs::StateDesc> kets;
-    if (dims_y) {
-      kets.assign(desc.begin() + nb0, desc.end());
-      desc.resize(nb0);
-    }
-    observe_descs(h, desc, size_t(i0), o, nullptr, so, sn, dims_y ? &kets : nullptr);
+  // a chunk's workspace comes from the arenas, recycled at its sync
+  template <class F>
+  void chunk(size_t, F&& mid) {
+    struct Run {
+      ObsBackend be;
+      obs::Traffic& tr;
+      bool ok() const { return true; }
+      void note(hipError_t e) {
+        if (e != hipSuccess) throw hbm::Error(3, std::string("observables: ") + hipGetErrorString(e));
+      }
+    } run{ObsBackend{E}, h->obs_tr};
+    Timer t(h, 9);
+    mid(run);
+    t.stop();
     E.sync();
   }
+  struct Stage {
+    hipStream_t st;
+    hbm::DBuf<double> buf;
+    double* p = nullptr;
+    Stage(hipStream_t st_, size_t n) : st(st_) {
+      buf.reserve(2 * n);
+      p = buf.p;
+    }
+    Stage(const Stage&) = delete;
+    ~Stage() { (void)hipStreamSynchronize(st); }  // (then buf goes)
+  };
+  Stage stage(size_t n, const char*) { return Stage(E.st, n); }
+};
+// an observable entry point: the guard around the shared front end
+template <class F>
+int observe_guard(hbm_engine* h, F f) {
+  return guard(h, [&] {
+    HbmFront a(h);
+    f(a);
+  });
 }
 }  // namespace
 
 int hbm_observe(hbm_engine* h, int which, const int* ts, int nt, const int* rows, int nrows, double* norm2,
                 double* occ, int* bond, double* ada, double* nn) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
-    const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
-    if (!ok) throw hbm::Error(4, "requested trajectory not available");
-    observe_check_rows(E, rows, nrows);
-    const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
-    std::vector<int> slots(nt);
-    for (int i = 0; i < nt; ++i) {
-      const int t = ts ? ts[i] : i;
-      if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
-      slots[i] = base + t;
-    }
-    if (nt == 0) return;
-    obs::Outputs o{norm2, occ, ada, nn, E.L, E.p, nrows, rows};
-    std::vector<double> tmp;
-    double* occ_buf = occ;
-    if (!occ && obs::want_of(o).occ) {
-      tmp.assign(size_t(nt) * E.L * E.p, 0.0);
-      occ_buf = tmp.data();
-    }
-    if (ada) std::fill(ada, ada + 2 * size_t(nt) * nrows * E.L, 0.0);
-    if (nn) std::fill(nn, nn + size_t(nt) * nrows * E.L, 0.0);
-    observe_slots(h, slots, 0, o, bond, occ_buf);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::observe(a, which, ts, nt, rows, nrows, norm2, occ, bond, ada, nn); });
 }
 
 int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* const* data, const int* rows, int nrows,
                        double* norm2, double* occ, int* bond, double* ada, double* nn) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
-    observe_check_rows(E, rows, nrows);
+  return observe_guard(h, [&](HbmFront& a) {
+    hbm::Engine& E = a.E;
+    obs::check_given(n, dims && data);
+    obs::observe_check_rows(a, rows, nrows);
     if (n == 0) return;
     const int nsq = (E.L + 1) * E.Q1;
     for (int i = 0; i < n; ++i) {
-      const int* d = dims + size_t(i) * nsq;
-      for (int j = 0; j < nsq; ++j)
-        if (d[j] < 0) throw hbm::Error(1, "negative bond dimension");
-      for (int q = 0; q < E.Q1; ++q)
-        if (d[q] != (q == 0 ? 1 : 0) || d[E.L * E.Q1 + q] != (q == E.Q ? 1 : 0))
-          throw hbm::Error(1, "bond 0 / bond L must be one state with q = 0 / q = Q");
-      E.set_caps(widest_of(E, d));
+      obs::staged_check(a, 1, dims + size_t(i) * nsq, -1);
+      E.set_caps(widest_of(E, dims + size_t(i) * nsq));
     }
-    obs::Outputs o{norm2, occ, ada, nn, E.L, E.p, nrows, rows};
+    const obs::Outputs o{norm2, occ, ada, nn, E.L, E.p, nrows, rows};
     std::vector<double> tmp;
-    double* occ_buf = occ;
-    if (!occ && obs::want_of(o).occ) {
-      tmp.assign(size_t(n) * E.L * E.p, 0.0);
-      occ_buf = tmp.data();
-    }
-    if (ada) std::fill(ada, ada + 2 * size_t(n) * nrows * E.L, 0.0);
-    if (nn) std::fill(nn, nn + size_t(n) * nrows * E.L, 0.0);
+    double* occ_buf = obs::observe_prepare(o, size_t(n), tmp);
     // staged in the scratch slots behind the trajectories, a batch at a time
     const int B = std::min(hbm_batch_states(h), n);
     const int sb = h->xih_base() + h->N;
@@ -3521,255 +3358,70 @@ int hbm_observe_states(hbm_engine* h, int n, const int* dims, const double* cons
         slots[i] = sb + i;
         E.upload_state(E.states[sb + i], dims + size_t(i0 + i) * nsq, data[i0 + i]);
       }
-      observe_slots(h, slots, size_t(i0), o, bond, occ_buf);
+      obs::observe_slots(a, slots, size_t(i0), o, bond, occ_buf);
     }
   });
 }
 
 int hbm_observe_spectrum(hbm_engine* h, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
                          int* sector) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
-    const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
-    if (!ok) throw hbm::Error(4, "requested trajectory not available");
-    const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
-    std::vector<int> slots(nt);
-    for (int i = 0; i < nt; ++i) {
-      const int t = ts ? ts[i] : i;
-      if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
-      slots[i] = base + t;
-    }
-    if (nt == 0 || (!entropy && !schmidt && !sector)) return;
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-    observe_slots(h, slots, 0, o, nullptr, nullptr, &so);
-  });
+  return observe_guard(
+      h, [&](HbmFront& a) { obs::observe_spectrum(a, which, ts, nt, wcap, entropy, schmidt, sector); });
 }
 
 int hbm_observe_spectrum_states(hbm_engine* h, int n, const int* dims, const double* const* data, int wcap,
                                 double* entropy, double* schmidt, int* sector) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
-    if (n == 0 || (!entropy && !schmidt && !sector)) return;
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-    staged_check(E, n, dims, so.weights() ? std::max(wcap, 0) : -1);
-    observe_staged(h, n, dims, data, o, &so, nullptr);
-  });
+  return observe_guard(
+      h, [&](HbmFront& a) { obs::observe_spectrum_states(a, n, dims, data, wcap, entropy, schmidt, sector); });
 }
-
-namespace {
-// the trajectory slots of a request (which / ts as hbm_observe)
-std::vector<int> trajectory_slots(hbm_engine* h, int which, const int* ts, int nt,
-                                  std::vector<unsigned long long>* ids) {
-  if (which < 0 || which > 2 || nt < 0) throw hbm::Error(1, "bad which / count");
-  const bool ok = (which == 0 && h->have_psi) || (which == 1 && h->have_xi) || (which == 2 && h->have_xih);
-  if (!ok) throw hbm::Error(4, "requested trajectory not available");
-  const int base = which == 0 ? h->psi_base() : (which == 1 ? h->xi_base() : h->xih_base());
-  std::vector<int> slots(nt);
-  if (ids) ids->resize(nt);
-  for (int i = 0; i < nt; ++i) {
-    const int t = ts ? ts[i] : i;
-    if (t < 0 || t >= h->N) throw hbm::Error(1, "t out of range");
-    slots[i] = base + t;
-    if (ids) (*ids)[i] = (unsigned long long)t;
-  }
-  return slots;
-}
-
-// every configuration has entries in 0..p-1 that add up to Q
-void check_configs(const hbm::Engine& E, const signed char* configs, int nconf, double* amp) {
-  if (nconf < 0 || (nconf > 0 && (!configs || !amp))) throw hbm::Error(1, "bad configurations / outputs");
-  for (int j = 0; j < nconf; ++j) {
-    int sum = 0;
-    for (int k = 0; k < E.L; ++k) {
-      const int v = configs[size_t(j) * E.L + k];
-      if (v < 0 || v >= E.p) throw hbm::Error(1, "a configuration entry outside 0..p-1");
-      sum += v;
-    }
-    if (sum != E.Q) throw hbm::Error(1, "a configuration that does not hold Q particles");
-  }
-}
-}  // namespace
 
 int hbm_sample(hbm_engine* h, int which, const int* ts, int nt, int nshots, unsigned long long seed,
                signed char* config, double* logp) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (nshots < 0 || (nshots > 0 && nt > 0 && !config)) throw hbm::Error(1, "bad shots / outputs");
-    std::vector<unsigned long long> ids;
-    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, &ids);
-    if (nt == 0 || nshots == 0) return;
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    obs::Snap sn;
-    sn.nper = nshots;
-    sn.seed = seed;
-    sn.ids = ids.data();
-    sn.config = config;
-    sn.val = logp;
-    observe_slots(h, slots, 0, o, nullptr, nullptr, nullptr, &sn);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::sample(a, which, ts, nt, nshots, seed, config, logp); });
 }
 
 int hbm_sample_states(hbm_engine* h, int n, const int* dims, const double* const* data, int nshots,
                       unsigned long long seed, signed char* config, double* logp) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
-    if (nshots < 0 || (nshots > 0 && n > 0 && !config)) throw hbm::Error(1, "bad shots / outputs");
-    if (n == 0 || nshots == 0) return;
-    staged_check(E, n, dims, -1);
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    std::vector<unsigned long long> ids(n);
-    for (int i = 0; i < n; ++i) ids[i] = (unsigned long long)i;
-    obs::Snap sn;
-    sn.nper = nshots;
-    sn.seed = seed;
-    sn.ids = ids.data();
-    sn.config = config;
-    sn.val = logp;
-    observe_staged(h, n, dims, data, o, nullptr, &sn);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::sample_states(a, n, dims, data, nshots, seed, config, logp); });
 }
 
 int hbm_fock_amplitudes(hbm_engine* h, int which, const int* ts, int nt, const signed char* configs, int nconf,
                         double* amp) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
-    check_configs(E, configs, nconf, amp);
-    if (nt == 0 || nconf == 0) return;
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    obs::Snap sn;
-    sn.nper = nconf;
-    sn.given = configs;
-    sn.val = amp;
-    observe_slots(h, slots, 0, o, nullptr, nullptr, nullptr, &sn);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::fock_amplitudes(a, which, ts, nt, configs, nconf, amp); });
 }
 
 int hbm_fock_amplitudes_states(hbm_engine* h, int n, const int* dims, const double* const* data,
                                const signed char* configs, int nconf, double* amp) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
-    check_configs(E, configs, nconf, amp);
-    if (n == 0 || nconf == 0) return;
-    staged_check(E, n, dims, -1);
-    const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    obs::Snap sn;
-    sn.nper = nconf;
-    sn.given = configs;
-    sn.val = amp;
-    observe_staged(h, n, dims, data, o, nullptr, &sn);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::fock_amplitudes_states(a, n, dims, data, configs, nconf, amp); });
 }
 
 int hbm_observe_moments(hbm_engine* h, int which, const int* ts, int nt, double* mom) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
-    if (nt == 0) return;
-    if (!mom) throw hbm::Error(1, "bad output");
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.mom = mom;
-    observe_slots(h, slots, 0, o, nullptr, nullptr);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::observe_moments(a, which, ts, nt, mom); });
 }
 
 int hbm_observe_moments_states(hbm_engine* h, int n, const int* dims, const double* const* data, double* mom) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data || !mom))) throw hbm::Error(1, "bad argument");
-    if (n == 0) return;
-    staged_check(E, n, dims, -1);
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.mom = mom;
-    observe_staged(h, n, dims, data, o, nullptr, nullptr);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::observe_moments_states(a, n, dims, data, mom); });
 }
 
 int hbm_observe_pairs(hbm_engine* h, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
                       double* occ, double* hop) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    const std::vector<int> sx = trajectory_slots(h, which_x, tx, npairs, nullptr);
-    const std::vector<int> sy = trajectory_slots(h, which_y, ty, npairs, nullptr);
-    if (npairs == 0 || (!ovl && !occ && !hop)) return;
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.povl = ovl;
-    o.pocc = occ;
-    o.phop = hop;
-    std::vector<obs::StateDesc> dx(npairs), dy(npairs);
-    for (int i = 0; i < npairs; ++i) {
-      dx[i] = obs_desc(E, E.states[sx[i]]);
-      dy[i] = obs_desc(E, E.states[sy[i]]);
-    }
-    observe_descs(h, dx, 0, o, nullptr, nullptr, nullptr, &dy);
-  });
+  return observe_guard(
+      h, [&](HbmFront& a) { obs::observe_pairs(a, which_x, tx, which_y, ty, npairs, ovl, occ, hop); });
 }
 
 int hbm_observe_pairs_states(hbm_engine* h, int n, const int* dims_x, const double* const* x, const int* dims_y,
                              const double* const* y, double* ovl, double* occ, double* hop) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims_x || !x || !dims_y || !y))) throw hbm::Error(1, "bad argument");
-    if (n == 0 || (!ovl && !occ && !hop)) return;
-    staged_check(E, n, dims_x, -1);
-    staged_check(E, n, dims_y, -1);
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.povl = ovl;
-    o.pocc = occ;
-    o.phop = hop;
-    observe_staged(h, n, dims_x, x, o, nullptr, nullptr, dims_y, y);
-  });
+  return observe_guard(
+      h, [&](HbmFront& a) { obs::observe_pairs_states(a, n, dims_x, x, dims_y, y, ovl, occ, hop); });
 }
-
-namespace {
-// the operators of a string request (f[nops][L][p][2], all finite) with their supports
-void string_request(const hbm::Engine& E, const double* f, int nops, obs::Strings& sr) {
-  if (nops < 0 || (nops > 0 && !f)) throw hbm::Error(1, "bad operator tables");
-  const size_t nf = 2 * size_t(nops) * E.L * E.p;
-  for (size_t j = 0; j < nf; ++j)
-    if (!std::isfinite(f[j])) throw hbm::Error(1, "a table entry is not finite");
-  sr.nops = nops;
-  sr.f = f;
-  sr.prepare(E.L, E.p);
-}
-}  // namespace
 
 int hbm_observe_strings(hbm_engine* h, int which, const int* ts, int nt, const double* f, int nops, double* out) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    const std::vector<int> slots = trajectory_slots(h, which, ts, nt, nullptr);
-    obs::Strings sr;
-    string_request(E, f, nops, sr);
-    if (nt == 0 || nops == 0) return;
-    if (!out) throw hbm::Error(1, "bad output");
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.str = &sr;
-    o.sout = out;
-    observe_slots(h, slots, 0, o, nullptr, nullptr);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::observe_strings(a, which, ts, nt, f, nops, out); });
 }
 
 int hbm_observe_strings_states(hbm_engine* h, int n, const int* dims, const double* const* data, const double* f,
                                int nops, double* out) {
-  return guard(h, [&] {
-    hbm::Engine& E = *h->E;
-    if (n < 0 || (n > 0 && (!dims || !data))) throw hbm::Error(1, "bad argument");
-    obs::Strings sr;
-    string_request(E, f, nops, sr);
-    if (n == 0 || nops == 0) return;
-    if (!out) throw hbm::Error(1, "bad output");
-    staged_check(E, n, dims, -1);
-    obs::Outputs o{nullptr, nullptr, nullptr, nullptr, E.L, E.p, 0, nullptr};
-    o.str = &sr;
-    o.sout = out;
-    observe_staged(h, n, dims, data, o, nullptr, nullptr);
-  });
+  return observe_guard(h, [&](HbmFront& a) { obs::observe_strings_states(a, n, dims, data, f, nops, out); });
 }
 
 int hbm_stats(hbm_engine* h, int kind, double* ms, long* launches, double* bytes, double* flops, long* steps) {

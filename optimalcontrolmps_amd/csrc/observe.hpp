@@ -38,6 +38,8 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -46,6 +48,12 @@
 #include "observe_sample.hpp"
 
 namespace obs {
+
+// a failed call: a status code of include/ocmps.h (OCG_EINVAL = 1 .. OCG_ENOMEM = 6) and its message
+struct Error : std::runtime_error {
+  int code;
+  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
 
 struct Blk {
   const double* p = nullptr;  // interleaved (re, im); null: block absent

@@ -24,6 +24,7 @@
 #include "params.hpp"
 #include "fast_plan.hpp"
 #include "observe.hpp"
+#include "observe_front.hpp"
 
 using ocg::Chain;
 using ocg::zc;
@@ -1800,13 +1801,11 @@ int ocg_get_state(ocg_ctx* c, int which, int t, int* dims, double* data, size_t 
 
 // ------------------------------------------------------------ observables
 // The LDS engine's side of ocg_observe: block descriptors of pool slots (a
-// slot holds the compact format, site k at site_base[k]) and observe.hpp's
-// driver on a workspace sized by its dry run, in chunks of at most half the
-// free device memory.  Reads the slots only.
+// slot holds the compact format, site k at site_base[k]) and the workspace,
+// backend and timing of a chunk, under observe_front.hpp's front end (the
+// checks, the chunks of at most half the free device memory, the entry
+// points' bodies).  Reads the slots only.
 static constexpr size_t kObsKeepBytes = size_t(256) << 20;
-static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn = nullptr,
-                         const std::vector<obs::StateDesc>* kets = nullptr);
 // the block descriptors of pool slots (and the bond dimensions into entry out0 + i of bond)
 static int slot_descs(ocg_ctx* c, const std::vector<int>& slots, size_t out0, int* bond,
                       std::vector<obs::StateDesc>& desc) {
@@ -1845,227 +1844,112 @@ static int slot_descs(ocg_ctx* c, const std::vector<int>& slots, size_t out0, in
   }
   return 0;
 }
-// With so the spectrum stages run too and their results go to *so; with sn the
-// snapshot launch follows the right sweep instead and its results go to sn's outputs.
-static int observe_slots(ocg_ctx* c, const std::vector<int>& slots, size_t out0, const obs::Outputs& o, int* bond,
-                         double* occ_buf, const obs::SpecOutputs* so = nullptr, obs::Snap* sn = nullptr) {
-  std::vector<obs::StateDesc> desc;
-  if (int rc = slot_descs(c, slots, out0, bond, desc)) return rc;
-  return observe_descs(c, desc, out0, o, occ_buf, so, sn);
+
+// a status of this file's helpers (its message already in c->err) as the front end's exception
+static void throw_status(ocg_ctx* c, int rc) {
+  if (rc) throw obs::Error(rc, c->err);
 }
 
-// the chunks of observe.hpp's driver over states described on the device (with kets: over the pairs
-// bra desc[i], ket (*kets)[i])
-static int observe_descs(ocg_ctx* c, const std::vector<obs::StateDesc>& desc, size_t out0, const obs::Outputs& o,
-                         double* occ_buf, const obs::SpecOutputs* so, obs::Snap* sn,
-                         const std::vector<obs::StateDesc>* kets) {
-  const OcgParams& P = c->P;
-  const int nst = int(desc.size());
-  obs::Want want = obs::want_of(o);
-  want.spec = so != nullptr;
-  if (!want.norm && !want.env() && !want.spec && !want.mom && !want.pair && !want.str && !sn) return 0;
-  if (want.str) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
-    if (wo > obs::kStringMaxOrder) return fail(c, OCG_ECAP, "strings: a bond sector above order 512");
+// this engine as observe_front.hpp sees it
+struct LdsFront {
+  ocg_ctx* c;
+  const int L, p, Q;
+  explicit LdsFront(ocg_ctx* c_) : c(c_), L(c_->P.L), p(c_->P.p), Q(c_->P.Q) {}
+  int N() const { return c->N; }
+  hipStream_t stream() const { return c->stream; }
+  bool have(int which) const { return which == 0 ? c->have_psi : which == 1 ? c->have_xi : c->have_xih; }
+  int base(int which) const { return which == 0 ? c->psi_base() : which == 1 ? c->xi_base() : c->xih_base(); }
+  void describe(const std::vector<int>& slots, size_t out0, int* bond, std::vector<obs::StateDesc>& desc) {
+    throw_status(c, slot_descs(c, slots, out0, bond, desc));
   }
-  if (sn) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
-    if (wo > obs::kSampleMaxOrder) return fail(c, OCG_ECAP, "snapshots: a bond sector above order 512");
-  }
-  if (want.pair) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) {
-      obs::widest(desc[i], P.L, P.Q1, wb, wo);
-      obs::widest((*kets)[i], P.L, P.Q1, wb, wo);
-    }
-    if (wo > obs::kPairMaxOrder) return fail(c, OCG_ECAP, "pairs: a bond sector above order 512");
-  }
-  if (want.mom) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
-    if (wo > obs::kEnergyMaxOrder) return fail(c, OCG_ECAP, "moments: a bond sector above order 512");
-  }
-  if (so) {
-    int wb = 0, wo = 0;
-    for (int i = 0; i < nst; ++i) obs::widest(desc[i], P.L, P.Q1, wb, wo);
-    if (so->weights() && so->wcap < wb)
-      return fail(c, OCG_ECAP, "wcap " + std::to_string(so->wcap) + " below the largest bond dimension " +
-                                   std::to_string(wb));
-    if (wo > obs::kEigMaxOrder) return fail(c, OCG_ECAP, "spectrum: a bond sector above order 512");
-  }
-  const std::vector<int> rows(o.rows, o.rows + o.nrows);
-  const std::vector<size_t> need = obs::workspace_needs(P.L, P.p, P.Q, desc, rows, want, sn, kets);
-  const size_t budget = obs::chunk_budget();
-  for (int i0 = 0; i0 < nst;) {
-    int i1 = i0;
-    size_t sum = 0;
-    while (i1 < nst && (i1 == i0 || sum + need[i1] <= budget)) sum += need[i1++];
-    if ((sn || want.mom || want.pair || want.str) && sum > budget)  // (the older calls leave a single state above the budget to the allocation)
-      return fail(c, OCG_ENOMEM, std::string(sn ? "snapshots" : want.pair ? "pairs" : want.str ? "strings" : "moments") +
-                                     ": the workspace of one " + (want.pair ? "pair" : "state") + " (" +
-                                     std::to_string(sum) + " B) exceeds the chunk budget");
-    std::vector<const obs::StateDesc*> S, SY;
-    std::vector<size_t> os;
-    for (int i = i0; i < i1; ++i) {
-      S.push_back(&desc[i]);
-      if (kets) SY.push_back(&(*kets)[i]);
-      os.push_back(out0 + i);
-    }
-    obs::RawBackend be;
-    // small workspaces stay with the context (an allocation and a free per call cost more than the kernels)
-    const bool keep = sum <= kObsKeepBytes;
-    if (keep && sum <= c->obs_cap) {
-      be.base = c->d_obs;
-    } else {
+  // A chunk's workspace: small ones stay with the context (an allocation and a free per call cost more
+  // than the kernels).  Leaving, it waits for the stream and frees what is not kept.
+  struct Workspace {
+    ocg_ctx* c;
+    char* p = nullptr;
+    const bool keep;
+    Workspace(ocg_ctx* c_, size_t bytes) : c(c_), keep(bytes <= kObsKeepBytes) {
+      if (keep && bytes <= c->obs_cap) {
+        p = c->d_obs;
+        return;
+      }
       if (keep && c->d_obs) {
         (void)hipFree(c->d_obs);
         c->d_obs = nullptr;
         c->obs_cap = 0;
       }
-      if (hipMalloc((void**)&be.base, sum) != hipSuccess) {
+      if (hipMalloc((void**)&p, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(c, OCG_ENOMEM,
-                    "observables: the workspace of one chunk (" + std::to_string(sum) + " B) does not fit");
+        throw obs::Error(OCG_ENOMEM,
+                         "observables: the workspace of one chunk (" + std::to_string(bytes) + " B) does not fit");
       }
       if (keep) {
-        c->d_obs = be.base;
-        c->obs_cap = sum;
+        c->d_obs = p;
+        c->obs_cap = bytes;
       }
     }
-    be.cap = sum;
-    be.st = c->stream;
-    std::vector<obs::Dest> dests;
-    obs::Traffic tr;
-    int rc = begin_kernel(c);
-    std::vector<double> res, ent, wts;
-    std::vector<int> status;
-    obs::Spec sp;
-    if (!rc) {
-      const double* d_out = obs::run_chunk(be, P.L, P.p, P.Q, S, os, rows, want, dests, tr, so ? &sp : nullptr, sn,
-                                           kets ? &SY : nullptr);
-      if (sn && be.ok()) be.note(sn->fetch(out0 + i0, S.size(), P.L, c->stream));
-      res.resize(2 * std::max<size_t>(dests.size(), 1));
-      if (be.ok() && !dests.empty())
-        be.note(hipMemcpyAsync(res.data(), d_out, sizeof(double) * 2 * dests.size(), hipMemcpyDeviceToHost,
-                               c->stream));
-      if (so && be.ok()) {  // only results leave the device: the weights when they are asked for
-        ent.resize(std::max<size_t>(S.size() * (P.L - 1), 1));
-        status.resize(std::max<size_t>(sp.nstatus, 1));
-        wts.resize(so->weights() ? std::max<size_t>(sp.nw, 1) : 0);
-        if (P.L > 1)
-          be.note(hipMemcpyAsync(ent.data(), sp.d_ent, sizeof(double) * S.size() * (P.L - 1),
-                                 hipMemcpyDeviceToHost, c->stream));
-        if (sp.nstatus)
-          be.note(hipMemcpyAsync(status.data(), sp.d_status, sizeof(int) * sp.nstatus, hipMemcpyDeviceToHost,
-                                 c->stream));
-        if (so->weights() && sp.nw)
-          be.note(hipMemcpyAsync(wts.data(), sp.d_w, sizeof(double) * sp.nw, hipMemcpyDeviceToHost, c->stream));
+    Workspace(const Workspace&) = delete;
+    ~Workspace() {
+      (void)hipStreamSynchronize(c->stream);
+      if (!keep) (void)hipFree(p);
+    }
+  };
+  template <class F>
+  void chunk(size_t bytes, F&& mid) {
+    struct Run {
+      obs::RawBackend be;  // (its queued uploads outlive the workspace's wait for the stream)
+      obs::Traffic tr;
+      bool ok() const { return be.ok(); }
+      void note(hipError_t e) { be.note(e); }
+    } run;
+    Workspace ws(c, bytes);
+    run.be.base = ws.p;
+    run.be.cap = bytes;
+    run.be.st = c->stream;
+    throw_status(c, begin_kernel(c));
+    mid(run);
+    throw_status(c, end_kernel(c, 9));  // synchronises the stream
+    if (!run.be.ok())
+      throw obs::Error(run.be.overflow ? OCG_ENOMEM : OCG_EHIP,
+                       run.be.overflow ? std::string("observables: workspace overflow")
+                                       : std::string("observables: ") + hipGetErrorString(run.be.err));
+    c->obs_tr.bytes += run.tr.bytes;
+    c->obs_tr.flops += run.tr.flops;
+    c->obs_tr.launches += run.tr.launches;
+  }
+  struct Stage {
+    hipStream_t st;
+    double* p = nullptr;
+    Stage(hipStream_t st_, size_t n, const char* what) : st(st_) {
+      if (hipMalloc((void**)&p, 16 * n) != hipSuccess) {
+        (void)hipGetLastError();
+        throw obs::Error(OCG_ENOMEM, std::string(what) + ": the staged states do not fit");
       }
-      rc = end_kernel(c, 9);  // synchronises the stream
-      if (!rc && !be.ok())
-        rc = fail(c, be.overflow ? OCG_ENOMEM : OCG_EHIP,
-                  be.overflow ? std::string("observables: workspace overflow")
-                              : std::string("observables: ") + hipGetErrorString(be.err));
     }
-    (void)hipStreamSynchronize(c->stream);
-    if (!keep) (void)hipFree(be.base);
-    if (rc) return rc;
-    c->obs_tr.bytes += tr.bytes;
-    c->obs_tr.flops += tr.flops;
-    c->obs_tr.launches += tr.launches;
-    if (so) {
-      for (size_t j = 0; j < sp.nstatus; ++j)
-        if (status[j]) return fail(c, OCG_ENUM, "spectrum: a Jacobi eigen block did not converge");
-      obs::scatter_spectrum(sp, S, os, P.L, P.Q1, ent.data(), wts.data(), *so);
+    Stage(const Stage&) = delete;
+    ~Stage() {
+      (void)hipStreamSynchronize(st);
+      (void)hipFree(p);
     }
-    obs::scatter(dests, res.data(), o, occ_buf);
-    if (o.nrows > 0 && (o.ada || o.nn))
-      for (int i = i0; i < i1; ++i) obs::diagonals(out0 + i, o, occ_buf);
-    i0 = i1;
+  };
+  Stage stage(size_t n, const char* what) { return Stage(c->stream, n, what); }
+};
+
+// an observable entry point of this engine: the front end's exceptions become the call's status
+template <class F>
+static int observe_guard(ocg_ctx* c, F f) {
+  try {
+    HIPCHK(c, hipSetDevice(c->device));
+    LdsFront a(c);
+    f(a);
+    return 0;
+  } catch (const obs::Error& e) {
+    return fail(c, e.code, e.what());
+  } catch (const std::bad_alloc& e) {
+    return fail(c, OCG_ENOMEM, std::string("host allocation failed: ") + e.what());
+  } catch (const std::exception& e) {
+    return fail(c, OCG_EHIP, e.what());
   }
-  return 0;
-}
-
-static int observe_check_rows(ocg_ctx* c, const int* rows, int nrows) {
-  if (nrows < 0 || (nrows > 0 && !rows)) return fail(c, OCG_EINVAL, "bad rows");
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 1 || rows[i] > c->P.L) return fail(c, OCG_EINVAL, "row (start site) out of 1..L");
-  return 0;
-}
-
-// zero the row outputs (entries j < i stay 0) and pick the occupation buffer
-static double* observe_prepare(const obs::Outputs& o, size_t n, std::vector<double>& tmp) {
-  if (o.ada) std::fill(o.ada, o.ada + 2 * n * o.nrows * o.L, 0.0);
-  if (o.nn) std::fill(o.nn, o.nn + n * o.nrows * o.L, 0.0);
-  if (o.occ || !obs::want_of(o).occ) return o.occ;
-  tmp.assign(n * o.L * o.p, 0.0);
-  return tmp.data();
-}
-
-// the dims of caller-supplied states, before anything is written (wcap >= 0: the
-// bond dimensions must fit it)
-static int staged_check(ocg_ctx* c, int n, const int* dims, int wcap) {
-  const OcgParams& P = c->P;
-  for (int i = 0; i < n; ++i) {
-    const int* d = dims + size_t(i) * P.nsq;
-    for (int j = 0; j < P.nsq; ++j)
-      if (d[j] < 0) return fail(c, OCG_EINVAL, "negative bond dimension");
-    for (int q = 0; q < P.Q1; ++q)
-      if (d[q] != (q == 0 ? 1 : 0) || d[P.L * P.Q1 + q] != (q == P.Q ? 1 : 0))
-        return fail(c, OCG_EINVAL, "bond 0 / bond L must be one state with q = 0 / q = Q");
-    for (int b = 1; b < P.L && wcap >= 0; ++b) {
-      long sum = 0;
-      for (int q = 0; q < P.Q1; ++q) sum += d[size_t(b) * P.Q1 + q];
-      if (sum > wcap) return fail(c, OCG_ECAP, "wcap below the largest bond dimension of the states");
-    }
-  }
-  return 0;
-}
-
-// Caller-supplied states staged a batch at a time in the compact interchange format
-// itself: its blocks are the contiguous row-major matrices the descriptors want, and a
-// sector may be larger than the Schmidt-rank bound of the pool slots (a padded or
-// over-parametrised state).
-// With dims_y / data_y the states are the bras of pairs and those the kets, staged behind them.
-static int observe_staged(ocg_ctx* c, int n, const int* dims, const double* const* data, const obs::Outputs& o,
-                          const obs::SpecOutputs* so, obs::Snap* sn, const char* what, const int* dims_y = nullptr,
-                          const double* const* data_y = nullptr) {
-  const OcgParams& P = c->P;
-  const int B = std::min(n, 64);
-  for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb0 = std::min(B, n - i0), nb = dims_y ? 2 * nb0 : nb0;
-    // entry i of the batch: state i0 + i, or for i >= nb0 the ket i0 + i - nb0
-    auto dims_of = [&](int i) { return i < nb0 ? dims + size_t(i0 + i) * P.nsq : dims_y + size_t(i0 + i - nb0) * P.nsq; };
-    auto data_of = [&](int i) { return i < nb0 ? data[i0 + i] : data_y[i0 + i - nb0]; };
-    std::vector<obs::StateDesc> desc(nb);
-    std::vector<size_t> at(nb + 1, 0);
-    for (int i = 0; i < nb; ++i) at[i + 1] = at[i] + ocg_mps_nelem(P.L, P.p, P.Q, dims_of(i));
-    double* d_st = nullptr;
-    if (hipMalloc((void**)&d_st, 16 * std::max<size_t>(at[nb], 1)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(c, OCG_ENOMEM, std::string(what) + ": the staged states do not fit");
-    }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < nb && e == hipSuccess; ++i) {
-      const int* d = dims_of(i);
-      if (at[i + 1] > at[i])
-        e = hipMemcpyAsync(d_st + 2 * at[i], data_of(i), 16 * (at[i + 1] - at[i]), hipMemcpyHostToDevice, c->stream);
-      obs::compact_desc(P.L, P.p, P.Q, d, d_st + 2 * at[i], desc[i]);
-    }
-    std::vector<obs::StateDesc> kets;
-    if (dims_y) {
-      kets.assign(desc.begin() + nb0, desc.end());
-      desc.resize(nb0);
-    }
-    int rc = e == hipSuccess ? observe_descs(c, desc, size_t(i0), o, nullptr, so, sn, dims_y ? &kets : nullptr)
-                             : fail(c, OCG_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_st);
-    if (rc) return rc;
-  }
-  return 0;
 }
 
 extern "C" {
@@ -2075,23 +1959,9 @@ int ocg_observe(ocg_ctx* c, int which, const int* ts, int nt, const int* rows, i
   if (!c) return OCG_EINVAL;
   if (c->hbm)
     return hb(c, hbm_observe(c->hbm, which, ts, nt, rows, nrows, norm2, occ, bond, corr_ada, corr_nn));
-  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
-  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
-  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
-  if (int rc = observe_check_rows(c, rows, nrows)) return rc;
-  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
-  std::vector<int> slots(nt);
-  for (int i = 0; i < nt; ++i) {
-    const int t = ts ? ts[i] : i;
-    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
-    slots[i] = base + t;
-  }
-  if (nt == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const obs::Outputs o{norm2, occ, corr_ada, corr_nn, c->P.L, c->P.p, nrows, rows};
-  std::vector<double> tmp;
-  double* occ_buf = observe_prepare(o, size_t(nt), tmp);
-  return observe_slots(c, slots, 0, o, bond, occ_buf);
+  return observe_guard(c, [&](LdsFront& a) {
+    obs::observe(a, which, ts, nt, rows, nrows, norm2, occ, bond, corr_ada, corr_nn);
+  });
 }
 
 int ocg_observe_states(ocg_ctx* c, int n, const int* dims, const double* const* data, const int* rows, int nrows,
@@ -2099,275 +1969,112 @@ int ocg_observe_states(ocg_ctx* c, int n, const int* dims, const double* const* 
   if (!c) return OCG_EINVAL;
   if (c->hbm)
     return hb(c, hbm_observe_states(c->hbm, n, dims, data, rows, nrows, norm2, occ, bond, corr_ada, corr_nn));
-  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
-  if (int rc = observe_check_rows(c, rows, nrows)) return rc;
-  if (n == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const OcgParams& P = c->P;
-  const obs::Outputs o{norm2, occ, corr_ada, corr_nn, P.L, P.p, nrows, rows};
-  std::vector<double> tmp;
-  double* occ_buf = observe_prepare(o, size_t(n), tmp);
-  // staged in the scratch slots after the trajectory slots, as ocg_step_batch, a batch at a time
-  const int base = 6 + 4 * c->N, B = std::min(n, 64);
-  if (int rc = ensure_slots(c, base + B)) return rc;
-  for (int i0 = 0; i0 < n; i0 += B) {
-    const int nb = std::min(B, n - i0);
-    std::vector<int> slots(nb);
-    for (int i = 0; i < nb; ++i) {
-      slots[i] = base + i;
-      if (int rc = upload_mps(c, slots[i], dims + size_t(i0 + i) * P.nsq, data[i0 + i])) return rc;
+  return observe_guard(c, [&](LdsFront& a) {
+    obs::check_given(n, dims && data);
+    obs::observe_check_rows(a, rows, nrows);
+    if (n == 0) return;
+    const OcgParams& P = c->P;
+    const obs::Outputs o{norm2, occ, corr_ada, corr_nn, P.L, P.p, nrows, rows};
+    std::vector<double> tmp;
+    double* occ_buf = obs::observe_prepare(o, size_t(n), tmp);
+    // staged in the scratch slots after the trajectory slots, as ocg_step_batch, a batch at a time
+    const int base = 6 + 4 * c->N, B = std::min(n, 64);
+    throw_status(c, ensure_slots(c, base + B));
+    for (int i0 = 0; i0 < n; i0 += B) {
+      const int nb = std::min(B, n - i0);
+      std::vector<int> slots(nb);
+      for (int i = 0; i < nb; ++i) {
+        slots[i] = base + i;
+        throw_status(c, upload_mps(c, slots[i], dims + size_t(i0 + i) * P.nsq, data[i0 + i]));
+      }
+      obs::observe_slots(a, slots, size_t(i0), o, bond, occ_buf);
     }
-    if (int rc = observe_slots(c, slots, size_t(i0), o, bond, occ_buf)) return rc;
-  }
-  return 0;
+  });
 }
 
 int ocg_observe_spectrum(ocg_ctx* c, int which, const int* ts, int nt, int wcap, double* entropy, double* schmidt,
                          int* sector) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_spectrum(c->hbm, which, ts, nt, wcap, entropy, schmidt, sector));
-  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
-  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
-  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
-  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
-  std::vector<int> slots(nt);
-  for (int i = 0; i < nt; ++i) {
-    const int t = ts ? ts[i] : i;
-    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
-    slots[i] = base + t;
-  }
-  if (nt == 0 || (!entropy && !schmidt && !sector)) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-  return observe_slots(c, slots, 0, o, nullptr, nullptr, &so);
+  return observe_guard(
+      c, [&](LdsFront& a) { obs::observe_spectrum(a, which, ts, nt, wcap, entropy, schmidt, sector); });
 }
 
 int ocg_observe_spectrum_states(ocg_ctx* c, int n, const int* dims, const double* const* data, int wcap,
                                 double* entropy, double* schmidt, int* sector) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_spectrum_states(c->hbm, n, dims, data, wcap, entropy, schmidt, sector));
-  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
-  if (n == 0 || (!entropy && !schmidt && !sector)) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const OcgParams& P = c->P;
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, P.L, P.p, 0, nullptr};
-  const obs::SpecOutputs so{entropy, schmidt, sector, wcap};
-  if (int rc = staged_check(c, n, dims, so.weights() ? std::max(wcap, 0) : -1)) return rc;
-  return observe_staged(c, n, dims, data, o, &so, nullptr, "spectrum");
-}
-
-// the trajectory slots of a request (which / ts as ocg_observe)
-static int trajectory_slots(ocg_ctx* c, int which, const int* ts, int nt, std::vector<int>& slots,
-                            std::vector<unsigned long long>* ids) {
-  if (which < 0 || which > 2 || nt < 0) return fail(c, OCG_EINVAL, "bad which / count");
-  const bool ok = (which == 0 && c->have_psi) || (which == 1 && c->have_xi) || (which == 2 && c->have_xih);
-  if (!ok) return fail(c, OCG_ESTATE, "requested trajectory not available");
-  const int base = which == 0 ? c->psi_base() : (which == 1 ? c->xi_base() : c->xih_base());
-  slots.resize(nt);
-  if (ids) ids->resize(nt);
-  for (int i = 0; i < nt; ++i) {
-    const int t = ts ? ts[i] : i;
-    if (t < 0 || t >= c->N) return fail(c, OCG_EINVAL, "t out of range");
-    slots[i] = base + t;
-    if (ids) (*ids)[i] = (unsigned long long)t;
-  }
-  return 0;
+  return observe_guard(
+      c, [&](LdsFront& a) { obs::observe_spectrum_states(a, n, dims, data, wcap, entropy, schmidt, sector); });
 }
 
 int ocg_sample(ocg_ctx* c, int which, const int* ts, int nt, int nshots, unsigned long long seed, signed char* config,
                double* logp) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_sample(c->hbm, which, ts, nt, nshots, seed, config, logp));
-  if (nshots < 0 || (nshots > 0 && nt > 0 && !config)) return fail(c, OCG_EINVAL, "bad shots / outputs");
-  std::vector<int> slots;
-  std::vector<unsigned long long> ids;
-  if (int rc = trajectory_slots(c, which, ts, nt, slots, &ids)) return rc;
-  if (nt == 0 || nshots == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  obs::Snap sn;
-  sn.nper = nshots;
-  sn.seed = seed;
-  sn.ids = ids.data();
-  sn.config = config;
-  sn.val = logp;
-  return observe_slots(c, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+  return observe_guard(c, [&](LdsFront& a) { obs::sample(a, which, ts, nt, nshots, seed, config, logp); });
 }
 
 int ocg_sample_states(ocg_ctx* c, int n, const int* dims, const double* const* data, int nshots,
                       unsigned long long seed, signed char* config, double* logp) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_sample_states(c->hbm, n, dims, data, nshots, seed, config, logp));
-  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
-  if (nshots < 0 || (nshots > 0 && n > 0 && !config)) return fail(c, OCG_EINVAL, "bad shots / outputs");
-  if (n == 0 || nshots == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = staged_check(c, n, dims, -1)) return rc;
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  std::vector<unsigned long long> ids(n);
-  for (int i = 0; i < n; ++i) ids[i] = (unsigned long long)i;
-  obs::Snap sn;
-  sn.nper = nshots;
-  sn.seed = seed;
-  sn.ids = ids.data();
-  sn.config = config;
-  sn.val = logp;
-  return observe_staged(c, n, dims, data, o, nullptr, &sn, "snapshots");
-}
-
-// every configuration has entries in 0..p-1 that add up to Q
-static int check_configs(ocg_ctx* c, const signed char* configs, int nconf, double* amp) {
-  if (nconf < 0 || (nconf > 0 && (!configs || !amp))) return fail(c, OCG_EINVAL, "bad configurations / outputs");
-  for (int j = 0; j < nconf; ++j) {
-    int sum = 0;
-    for (int k = 0; k < c->P.L; ++k) {
-      const int v = configs[size_t(j) * c->P.L + k];
-      if (v < 0 || v >= c->P.p) return fail(c, OCG_EINVAL, "a configuration entry outside 0..p-1");
-      sum += v;
-    }
-    if (sum != c->P.Q) return fail(c, OCG_EINVAL, "a configuration that does not hold Q particles");
-  }
-  return 0;
+  return observe_guard(c, [&](LdsFront& a) { obs::sample_states(a, n, dims, data, nshots, seed, config, logp); });
 }
 
 int ocg_fock_amplitudes(ocg_ctx* c, int which, const int* ts, int nt, const signed char* configs, int nconf,
                         double* amp) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_fock_amplitudes(c->hbm, which, ts, nt, configs, nconf, amp));
-  std::vector<int> slots;
-  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
-  if (int rc = check_configs(c, configs, nconf, amp)) return rc;
-  if (nt == 0 || nconf == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  obs::Snap sn;
-  sn.nper = nconf;
-  sn.given = configs;
-  sn.val = amp;
-  return observe_slots(c, slots, 0, o, nullptr, nullptr, nullptr, &sn);
+  return observe_guard(c, [&](LdsFront& a) { obs::fock_amplitudes(a, which, ts, nt, configs, nconf, amp); });
 }
 
 int ocg_fock_amplitudes_states(ocg_ctx* c, int n, const int* dims, const double* const* data,
                                const signed char* configs, int nconf, double* amp) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_fock_amplitudes_states(c->hbm, n, dims, data, configs, nconf, amp));
-  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
-  if (int rc = check_configs(c, configs, nconf, amp)) return rc;
-  if (n == 0 || nconf == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = staged_check(c, n, dims, -1)) return rc;
-  const obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  obs::Snap sn;
-  sn.nper = nconf;
-  sn.given = configs;
-  sn.val = amp;
-  return observe_staged(c, n, dims, data, o, nullptr, &sn, "amplitudes");
+  return observe_guard(c, [&](LdsFront& a) { obs::fock_amplitudes_states(a, n, dims, data, configs, nconf, amp); });
 }
 
 int ocg_observe_moments(ocg_ctx* c, int which, const int* ts, int nt, double* mom) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_moments(c->hbm, which, ts, nt, mom));
-  std::vector<int> slots;
-  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
-  if (nt == 0) return 0;
-  if (!mom) return fail(c, OCG_EINVAL, "bad output");
-  HIPCHK(c, hipSetDevice(c->device));
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.mom = mom;
-  return observe_slots(c, slots, 0, o, nullptr, nullptr);
+  return observe_guard(c, [&](LdsFront& a) { obs::observe_moments(a, which, ts, nt, mom); });
 }
 
 int ocg_observe_moments_states(ocg_ctx* c, int n, const int* dims, const double* const* data, double* mom) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_moments_states(c->hbm, n, dims, data, mom));
-  if (n < 0 || (n > 0 && (!dims || !data || !mom))) return fail(c, OCG_EINVAL, "bad argument");
-  if (n == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = staged_check(c, n, dims, -1)) return rc;
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.mom = mom;
-  return observe_staged(c, n, dims, data, o, nullptr, nullptr, "moments");
+  return observe_guard(c, [&](LdsFront& a) { obs::observe_moments_states(a, n, dims, data, mom); });
 }
 
 int ocg_observe_pairs(ocg_ctx* c, int which_x, const int* tx, int which_y, const int* ty, int npairs, double* ovl,
                       double* occ, double* hop) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_pairs(c->hbm, which_x, tx, which_y, ty, npairs, ovl, occ, hop));
-  std::vector<int> sx, sy;
-  if (int rc = trajectory_slots(c, which_x, tx, npairs, sx, nullptr)) return rc;
-  if (int rc = trajectory_slots(c, which_y, ty, npairs, sy, nullptr)) return rc;
-  if (npairs == 0 || (!ovl && !occ && !hop)) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.povl = ovl;
-  o.pocc = occ;
-  o.phop = hop;
-  std::vector<obs::StateDesc> dx, dy;
-  if (int rc = slot_descs(c, sx, 0, nullptr, dx)) return rc;
-  if (int rc = slot_descs(c, sy, 0, nullptr, dy)) return rc;
-  return observe_descs(c, dx, 0, o, nullptr, nullptr, nullptr, &dy);
+  return observe_guard(
+      c, [&](LdsFront& a) { obs::observe_pairs(a, which_x, tx, which_y, ty, npairs, ovl, occ, hop); });
 }
 
 int ocg_observe_pairs_states(ocg_ctx* c, int n, const int* dims_x, const double* const* x, const int* dims_y,
                              const double* const* y, double* ovl, double* occ, double* hop) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_pairs_states(c->hbm, n, dims_x, x, dims_y, y, ovl, occ, hop));
-  if (n < 0 || (n > 0 && (!dims_x || !x || !dims_y || !y))) return fail(c, OCG_EINVAL, "bad argument");
-  if (n == 0 || (!ovl && !occ && !hop)) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = staged_check(c, n, dims_x, -1)) return rc;
-  if (int rc = staged_check(c, n, dims_y, -1)) return rc;
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.povl = ovl;
-  o.pocc = occ;
-  o.phop = hop;
-  return observe_staged(c, n, dims_x, x, o, nullptr, nullptr, "pairs", dims_y, y);
-}
-
-// the operators of a string request (f[nops][L][p][2], all finite) with their supports
-static int string_request(ocg_ctx* c, const double* f, int nops, obs::Strings& sr) {
-  if (nops < 0 || (nops > 0 && !f)) return fail(c, OCG_EINVAL, "bad operator tables");
-  const size_t nf = 2 * size_t(nops) * c->P.L * c->P.p;
-  for (size_t j = 0; j < nf; ++j)
-    if (!std::isfinite(f[j])) return fail(c, OCG_EINVAL, "a table entry is not finite");
-  sr.nops = nops;
-  sr.f = f;
-  sr.prepare(c->P.L, c->P.p);
-  return 0;
+  return observe_guard(
+      c, [&](LdsFront& a) { obs::observe_pairs_states(a, n, dims_x, x, dims_y, y, ovl, occ, hop); });
 }
 
 int ocg_observe_strings(ocg_ctx* c, int which, const int* ts, int nt, const double* f, int nops, double* out) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_strings(c->hbm, which, ts, nt, f, nops, out));
-  std::vector<int> slots;
-  if (int rc = trajectory_slots(c, which, ts, nt, slots, nullptr)) return rc;
-  obs::Strings sr;
-  if (int rc = string_request(c, f, nops, sr)) return rc;
-  if (nt == 0 || nops == 0) return 0;
-  if (!out) return fail(c, OCG_EINVAL, "bad output");
-  HIPCHK(c, hipSetDevice(c->device));
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.str = &sr;
-  o.sout = out;
-  return observe_slots(c, slots, 0, o, nullptr, nullptr);
+  return observe_guard(c, [&](LdsFront& a) { obs::observe_strings(a, which, ts, nt, f, nops, out); });
 }
 
 int ocg_observe_strings_states(ocg_ctx* c, int n, const int* dims, const double* const* data, const double* f,
                                int nops, double* out) {
   if (!c) return OCG_EINVAL;
   if (c->hbm) return hb(c, hbm_observe_strings_states(c->hbm, n, dims, data, f, nops, out));
-  if (n < 0 || (n > 0 && (!dims || !data))) return fail(c, OCG_EINVAL, "bad argument");
-  obs::Strings sr;
-  if (int rc = string_request(c, f, nops, sr)) return rc;
-  if (n == 0 || nops == 0) return 0;
-  if (!out) return fail(c, OCG_EINVAL, "bad output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = staged_check(c, n, dims, -1)) return rc;
-  obs::Outputs o{nullptr, nullptr, nullptr, nullptr, c->P.L, c->P.p, 0, nullptr};
-  o.str = &sr;
-  o.sout = out;
-  return observe_staged(c, n, dims, data, o, nullptr, nullptr, "strings");
+  return observe_guard(c, [&](LdsFront& a) { obs::observe_strings_states(a, n, dims, data, f, nops, out); });
 }
 
 int ocg_kernel_stats(ocg_ctx* c, int kind, double* total_ms, long* launches, double* alg_bytes, double* alg_flops,

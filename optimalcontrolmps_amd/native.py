@@ -46,10 +46,10 @@ def build_native(force: bool = False, nt: int | None = None, verbose: bool = Fal
         "ocmps": ["ocmps.hip", "engine.hpp", "engine_device.hpp", "kernels.hpp", "params.hpp", "hbm.hpp",
                   "fast.hpp", "fast_plan.hpp", "fast_chain.hpp", "fast_overlap.hpp", "observe.hpp",
                   "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp",
-                  "observe_string.hpp"],
+                  "observe_string.hpp", "observe_front.hpp"],
         "hbm": ["hbm.hip", "hbm.hpp", "hbm_device.hpp", "hbm_eig.hpp", "hbm_coop.hpp", "observe.hpp",
                 "observe_eig.hpp", "observe_sample.hpp", "observe_energy.hpp", "observe_pair.hpp",
-                "observe_string.hpp"],
+                "observe_string.hpp", "observe_front.hpp"],
     }
     tag = f"nt{int(nt)}" if nt else "prod"
     objs, procs = [], []
