@@ -86,11 +86,24 @@ int ocg_get_info_sz(const ocg_ctx* ctx, ocg_info* info, size_t info_size);
  * 6 ocg_sample, ocg_sample_states, ocg_fock_amplitudes, ocg_fock_amplitudes_states;
  * 7 ocg_observe_moments, ocg_observe_moments_states; added within 7 (no existing
  * entry point or struct changed): ocg_observe_pairs, ocg_observe_pairs_states;
- * ocg_observe_strings, ocg_observe_strings_states. */
+ * ocg_observe_strings, ocg_observe_strings_states; ocg_set_potential,
+ * ocg_get_potential. */
 #define OCG_ABI_VERSION 7
 int ocg_abi_version(void);
 /* BH_tDMRG::setTstep (src/BH_tDMRG.cpp:61-65) */
 int ocg_set_tstep(ocg_ctx* ctx, double tstep);
+
+/* Static site potential sum_k eps_k n_k (trap, tilt, superlattice, disorder;
+ * DESIGN.md §15).  eps points to L doubles (site 1 first) or is NULL to clear
+ * it; all zeros is the same as NULL.  NaN / inf: OCG_EINVAL.  It applies to
+ * every later call that steps a state, in real and in imaginary time, on both
+ * engines: one step from u_from to u_to over tau = +-tstep is
+ * D_to G_odd G_even D_from with D_x = prod_k exp(-i tau [u_x n_k (n_k - 1) / 4
+ * + eps_k n_k / 2]).  dH/dU is unchanged.  Setting it drops the device
+ * trajectories like ocg_set_tstep.  ocg_get_potential writes L doubles (zeros
+ * when none is set).  (Additions within ABI version 7.) */
+int ocg_set_potential(ocg_ctx* ctx, const double* eps);
+int ocg_get_potential(const ocg_ctx* ctx, double* eps);
 /* number of complex elements of an MPS with the given dims */
 size_t ocg_mps_nelem(int L, int p, int Q, const int* dims);
 

@@ -49,6 +49,9 @@ struct OcgParams {
                             // row overlaps of getHessian run on the general contraction
   int ovl_bytes;            // LDS of the padded overlap (k_row_overlaps_pad; <= fast_off)
   int ovl_dh_bytes;         // LDS of the padded <x|y> / <x|dH|y> pairs (k_overlaps_pad)
+  const double* eph;        // static site potential, or null: none set.  2 L p complex
+                            // (re, im) half-phases of the current dt / time mode, [dir][k-1][n] =
+                            // exp(-i tau eps_k n / 2) (imag: exp(-tau eps_k n / 2)), dir 0: tau = +dt, 1: -dt
 };
 #define OCG_ERR_JACOBI 1
 #define OCG_ERR_WATCHDOG 2

@@ -359,6 +359,7 @@ struct Chain {
   bool phit = false;  // the current slot's key matched (uniform)
   double ph_u = __builtin_nan("");  // control value of PH[p..2p) (NaN: none yet)
   int ph_dir = -1;
+  const zc* eph = nullptr;  // this step's direction of the site-potential half-phases P.eph, or null (uniform)
   unsigned long long pf_last = 0;
   int pf_cur = 0;
   int pf_gauge = 0;  // profile build: cycles inside gauge moves also go to PROF[31]
@@ -651,6 +652,21 @@ struct Chain {
     sync();
   }
 
+  // the same with a table in global memory (the site-potential half-phases of site k)
+  __device__ OCG_INLINE void site_phase_g(int k, const zc* ph) {
+    pf(9);
+    const LDS int* B = boff(k);
+    if (w0) qstarts(B);
+    sync();
+    const int tot = B[SEG];
+    for (int e = tid; e < tot; e += NT) {
+      int q, n, o;
+      find_qn(B, e, q, n, o);
+      site(k)[e] = cmul(site(k)[e], ph[n]);
+    }
+    sync();
+  }
+
   // ------------------------------------------------------------- Θ
   // Two-site tensor for bond (i1, i1+1), blocks by middle QN q:
   //   rows (n1, a in bond i1-1 sector q-n1), cols (n2, c in bond i1+1 sector q+n2)
@@ -734,6 +750,17 @@ struct Chain {
     lzp gt = GT + (forward ? 0 : P.gtotal);
     lzp UF = PH;
     lzp UT = PH + p;
+    // site potential: the half-phases of sites i1, i2 join every U half-phase of those sites
+    const zc* e1 = eph ? eph + (i1 - 1) * p : nullptr;
+    const zc* e2 = eph ? e1 + p : nullptr;
+    auto uu = [&](lzp U, int n1, int n2) {
+      zc f = cmul(U[n1], U[n2]);
+      return e1 ? cmul(f, cmul(e1[n1], e2[n2])) : f;
+    };
+    auto u2 = [&](lzp U, int n2) {
+      zc f = U[n2];
+      return e1 ? cmul(f, e2[n2]) : f;
+    };
     const int tot = ISCAL[I_THT];
     if (phit) {
       const LDS int* ga = ps + pl.GA;
@@ -746,12 +773,12 @@ struct Chain {
         for (int x = 0; x < sz; ++x) {
           const int n1 = lo + x, n2 = D - n1;
           zc z = TH[(unsigned(gd[1 + (x >> 1)]) >> (16 * (x & 1))) & 0xffff];
-          if (mode == 0) z = cmul(z, cmul(UF[n1], UF[n2]));
-          else if (lonely & 2) z = cmul(z, UF[n2]);
+          if (mode == 0) z = cmul(z, uu(UF, n1, n2));
+          else if (lonely & 2) z = cmul(z, u2(UF, n2));
           cacc(acc, g[x], z);
         }
-        if (mode == 1) acc = cmul(acc, cmul(UT[a1], UT[a2]));
-        else if (lonely & 1) acc = cmul(acc, UT[a2]);
+        if (mode == 1) acc = cmul(acc, uu(UT, a1, a2));
+        else if (lonely & 1) acc = cmul(acc, u2(UT, a2));
         X[e] = acc;
       }
       sync();
@@ -782,16 +809,16 @@ struct Chain {
           const int ro = TRO[qs * p + n1] - TRO[qs * p], co = TCO[qs * p + n2] - TCO[qs * p];
           const int ad = THO[qs] + (ro + ia) * THC[qs] + co + ic;
           zc z = TH[ad];
-          if (mode == 0) z = cmul(z, cmul(UF[n1], UF[n2]));
-          else if (lonely & 2) z = cmul(z, UF[n2]);
+          if (mode == 0) z = cmul(z, uu(UF, n1, n2));
+          else if (lonely & 2) z = cmul(z, u2(UF, n2));
           cacc(acc, g[x], z);
           if (rr) {
             pk |= ad << (16 * (x & 1));
             if ((x & 1) || x + 1 == sz) { gd[1 + (x >> 1)] = pk; pk = 0; }
           }
         }
-        if (mode == 1) acc = cmul(acc, cmul(UT[a1], UT[a2]));
-        else if (lonely & 1) acc = cmul(acc, UT[a2]);
+        if (mode == 1) acc = cmul(acc, uu(UT, a1, a2));
+        else if (lonely & 1) acc = cmul(acc, u2(UT, a2));
         X[e] = acc;
       }
     }
@@ -2199,6 +2226,7 @@ struct Chain {
     }
     ph_u = uto;
     ph_dir = forward;
+    eph = P.eph ? (const zc*)P.eph + (forward ? 0 : L * p) : nullptr;
     // the lonely U_from on site L of an odd chain (:133-136) is applied by the
     // gate (L-1, L) (apply_gate lonely & 2)
     int centre = 1, gslot = 0;
@@ -2221,6 +2249,7 @@ struct Chain {
       if (more && (i2 == ni1 || i1 == ni2)) movingFromLeft = false;
     }
     // lonely U_to on site 1 (:222-223), then psi.normalize() (:228)
+    if (eph) site_phase_g(1, eph);  // its site-potential half-phase
     if (centre != 1) {
       // the phase is diagonal in site 1's physical index (commutes with the
       // gauge); the norm of the MPS is the norm of the centre site

@@ -817,6 +817,24 @@ struct FastChain {
     c = fma(z, pc, 1.0);
   }
 
+  // Static site potential: E = prod_k exp(-i tau eps_k n_k / 2) over the whole
+  // padded MPS, each element times the half-phase of its site and physical index (ep: this
+  // direction's L p table of P.eph).  E is diagonal in the physical indices, so it keeps every
+  // site's orthonormality and every bond; padded zeros stay zeros.
+  __device__ OCG_INLINE void potential_pass(const zc* ep) {
+    const int p = P.p;
+#pragma unroll
+    for (int it = 0; it < fastp::kItMps; ++it) {
+      const int x = lane + 64 * it;
+      if (x < np) {
+        const int b = PL[o_ls + 4 * x + 1] & 0xffff;
+        const int v = PL[o_blk + 4 * b];  // k | q << 8 | n << 16
+        MP[x] = cmul(MP[x], ep[((v & 255) - 1) * p + (v >> 16)]);
+      }
+    }
+    wsync();
+  }
+
   // ------------------------------------------------------------- step
   // BH_tDMRG::step (src/BH_tDMRG.cpp:111-125) + doStep (:127-230), as Chain::step
   // (final_gauge = false: the closing position(1) is skipped, the centre stays on
@@ -862,6 +880,9 @@ struct FastChain {
     ph_u = uto;
     ph_dir = forward;
     wsync();
+    // step_eps = E step_0 E: one pass before the sweep and one after it (none without a potential)
+    const zc* ep = P.eph ? (const zc*)P.eph + (forward ? 0 : P.L * p) : nullptr;
+    if (ep) potential_pass(ep);
     for (int o = 0; o < nops; ++o) {
       const LDS int* oh = PL + PL[kHOps + o];
       const i4 h0 = ld4(oh), h1 = ld4(oh + 4);
@@ -887,6 +908,7 @@ struct FastChain {
     const int s1a = PL[o_site + 1], s1b = PL[o_site + 2];
     for (int x = s1a + lane; x < s1b; x += 64) MP[x] = cmul(MP[x], PH[p + PL[o_siten + x - s1a]]);
     wsync();
+    if (ep) potential_pass(ep);
     const int ca = PL[o_site + centre], cb = PL[o_site + centre + 1];
     double acc = 0.0;
     zc v[kItMps];

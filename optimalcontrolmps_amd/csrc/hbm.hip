@@ -184,6 +184,7 @@ struct Engine {
   // device
   hipStream_t st = nullptr;
   GateConst gcst{};
+  std::vector<double> eps;  // static site potential eps_k (L entries), empty: none
   DBuf<z> d_gf, d_gb;
   DBuf<z> chain_pool, chain_pool_w;
   int nchain_cap = 0, nchain_cap_w = 0;
@@ -1689,7 +1690,8 @@ struct Engine {
           if (o < 0) continue;
           z* b = cs[i]->site(k) + o;
           CTask c = ctask(b, b, d(k - 1, q), ld, ld, ld);
-          const double a = -0.25 * u[i] * tau[i] * n * (n - 1);
+          double a = -0.25 * u[i] * tau[i] * n * (n - 1);
+          if (!eps.empty()) a -= 0.5 * eps[k - 1] * tau[i] * n;  // the site's potential half-phase
           c.f = gcst.imag ? mk(std::exp(a), 0.0) : mk(std::cos(a), std::sin(a));
           if (inv_norm) c.f = mk(c.f.x * (*inv_norm)[i], c.f.y * (*inv_norm)[i]);
           ct.push_back(c);
@@ -1901,7 +1903,13 @@ struct Engine {
     const GateChain* dgc = upload(gc);
     const GateTask* dt_ = upload(tasks);
     const long long blocks = std::min<long long>((tot + NT - 1) / NT, 8192);
-    hipLaunchKernelGGL(k_gate, dim3(unsigned(blocks)), dim3(NT), 0, st, dt_, int(tasks.size()), tot, dgc, gcst,
+    GateConst gk = gcst;
+    if (!eps.empty()) {
+      gk.has_eps = 1;
+      gk.e1 = eps[i1 - 1];
+      gk.e2 = eps[i1];
+    }
+    hipLaunchKernelGGL(k_gate, dim3(unsigned(blocks)), dim3(NT), 0, st, dt_, int(tasks.size()), tot, dgc, gk,
                        d_gf.p, d_gb.p);
     HCK(hipGetLastError());
   }
@@ -2645,6 +2653,14 @@ int hbm_set_tstep(hbm_engine* h, double tstep, const std::vector<double>& gf, co
     h->gf = gf;
     h->gb = gb;
     ++h->gates_version;
+  });
+}
+
+int hbm_set_potential(hbm_engine* h, const double* eps) {
+  return guard(h, [&] {
+    if (eps) h->E->eps.assign(eps, eps + h->E->L);
+    else h->E->eps.clear();
+    h->have_psi = h->have_xi = h->have_xih = false;
   });
 }
 
@@ -3584,6 +3600,7 @@ hbm::Engine& pipe_worker(hbm_engine* h, int k) {
   }
   W->dt = E.dt;
   W->gcst.imag = 0;
+  W->eps = E.eps;
   return *W;
 }
 // OCG_PIPE_DEBUG=1: progress lines of the three stages on stderr (diagnostic)

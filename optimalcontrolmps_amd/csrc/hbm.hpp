@@ -19,6 +19,8 @@ const char* hbm_last_error(const hbm_engine* h);
 size_t hbm_mps_max_nelem(const hbm_engine* h);
 int hbm_set_tstep(hbm_engine* h, double tstep, const std::vector<double>& gf, const std::vector<double>& gb,
                   const int* glo, const int* gsz, const int* goff, int gtotal);
+// static site potential eps[L] of every later step (null: none); drops the device trajectories
+int hbm_set_potential(hbm_engine* h, const double* eps);
 // swap the step's gates and time mode (imag: exp(-dt H)) without touching the
 // device trajectories (ocg_imag_steps switches in and back out)
 int hbm_swap_gates(hbm_engine* h, int imag, double tstep, const std::vector<double>& gf,

@@ -259,6 +259,10 @@ struct GateTask {
 struct GateConst {
   int p, Q1, glo[24], gsz[24], goff[24];
   int imag;  // imaginary-time steps (ground-state preparation)
+  // static site potential: the site energies of this gate's two sites
+  // (has_eps = 0: none set, the phases are those of the homogeneous chain)
+  int has_eps;
+  double e1, e2;
 };
 // exp(-i 0.25 u tau n (n-1)) (BH_tDMRG::initUGates, src/BH_tDMRG.cpp:83-87);
 // imaginary time: exp(-0.25 u tau n (n-1))
@@ -266,6 +270,14 @@ __device__ __forceinline__ z uphase(double u, double tau, int n, int imag) {
   if (imag) return mk(exp(-0.25 * u * tau * double(n * (n - 1))), 0.0);
   double s, c;
   sincos(-0.25 * u * tau * double(n * (n - 1)), &s, &c);
+  return mk(c, s);
+}
+// the same with the half-phase of a site energy e joined: exp(-i tau [u n (n-1) / 4 + e n / 2])
+__device__ __forceinline__ z uphase(double u, double tau, int n, int imag, double e) {
+  const double a = -0.25 * u * tau * double(n * (n - 1)) - 0.5 * e * tau * double(n);
+  if (imag) return mk(exp(a), 0.0);
+  double s, c;
+  sincos(a, &s, &c);
   return mk(c, s);
 }
 __global__ __launch_bounds__(NT) void k_gate(const GateTask* __restrict__ tasks, int ntask, long long total,
@@ -286,13 +298,22 @@ __global__ __launch_bounds__(NT) void k_gate(const GateTask* __restrict__ tasks,
     const int* co = C.tab + 2 * Q1 + Q1 * p;
     z v[12], w[12];
     size_t addr[12];
+    // phase of (site 1: n1, site 2: n2) at control u; n1 < 0: site 2 alone
+    auto ph = [&](double u, int n1, int n2) {
+      if (gc.has_eps) {
+        const z b = uphase(u, C.tau, n2, gc.imag, gc.e2);
+        return n1 < 0 ? b : zmul(uphase(u, C.tau, n1, gc.imag, gc.e1), b);
+      }
+      const z b = uphase(u, C.tau, n2, gc.imag);
+      return n1 < 0 ? b : zmul(uphase(u, C.tau, n1, gc.imag), b);
+    };
     for (int y = 0; y < sz; ++y) {
       const int n1 = lo + y, n2 = D - n1, q = T.ql + n1;
       const int r0 = (q < Q1) ? ro[q * p + n1] : -1, c0 = (q < Q1) ? co[q * p + n2] : -1;
       if (r0 < 0 || c0 < 0) { addr[y] = ~size_t(0); v[y] = mk(0, 0); continue; }
       addr[y] = (size_t)thoff[q] + (size_t)(r0 + a) * tC[q] + c0 + c;
       z t = C.th[addr[y]];
-      if (C.mode == 0) t = zmul(t, zmul(uphase(C.uf, C.tau, n1, gc.imag), uphase(C.uf, C.tau, n2, gc.imag)));
+      if (C.mode == 0) t = zmul(t, ph(C.uf, n1, n2));
       v[y] = t;
     }
     const z* G = (C.fwd ? gf : gb) + gc.goff[D];
@@ -300,8 +321,8 @@ __global__ __launch_bounds__(NT) void k_gate(const GateTask* __restrict__ tasks,
       z s = mk(0, 0);
       for (int xx = 0; xx < sz; ++xx) s = zadd(s, zmul(G[y * sz + xx], v[xx]));
       const int n1 = lo + y, n2 = D - n1;
-      if (C.mode == 1) s = zmul(s, zmul(uphase(C.ut, C.tau, n1, gc.imag), uphase(C.ut, C.tau, n2, gc.imag)));
-      else if (C.lonely) s = zmul(s, uphase(C.ut, C.tau, n2, gc.imag));
+      if (C.mode == 1) s = zmul(s, ph(C.ut, n1, n2));
+      else if (C.lonely) s = zmul(s, ph(C.ut, -1, n2));
       w[y] = s;
     }
     for (int y = 0; y < sz; ++y)

@@ -278,6 +278,8 @@ struct ocg_ctx {
   int* d_fplan = nullptr;     // plan image of the one-wave padded chain (null: off)
   int* d_oplan = nullptr;     // overlap plan of the padded layout (null: off)
   std::string fast_why;       // why it is off
+  std::vector<double> eps;    // static site potential eps_k (empty: none set)
+  double* d_eph = nullptr;    // its half-phase table (OcgParams::eph), rebuilt with the gates
   // trajectory state
   int N = 0;
   std::vector<double> u_psi, u_xi;  // controls of the device psi_t / xi_t (empty: none)
@@ -320,6 +322,13 @@ static int upload_gates(ocg_ctx* c) {
   }
   HIPCHK(c, hipMemcpyAsync(c->d_gf, gf.data(), sizeof(zc) * off, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_gb, gb.data(), sizeof(zc) * off, hipMemcpyHostToDevice, c->stream));
+  // the site potential's half-phases depend on dt and the time mode like the gates
+  if (!c->eps.empty()) {
+    const std::vector<double> t = ocg_host::potential_phases(c->P, c->eps);
+    if (!c->d_eph) HIPCHK(c, hipMalloc(&c->d_eph, sizeof(double) * t.size()));
+    HIPCHK(c, hipMemcpyAsync(c->d_eph, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  c->P.eph = c->eps.empty() ? nullptr : c->d_eph;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -798,6 +807,7 @@ int ocg_destroy(ocg_ctx* c) {
   if (c->d_rnorm) (void)hipFree(c->d_rnorm);
   if (c->d_idx2) (void)hipFree(c->d_idx2);
   if (c->d_fplan) (void)hipFree(c->d_fplan);
+  if (c->d_eph) (void)hipFree(c->d_eph);
   if (c->d_oplan) (void)hipFree(c->d_oplan);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   for (auto& e : c->evh)
@@ -873,6 +883,30 @@ int ocg_set_tstep(ocg_ctx* c, double tstep) {
     return hb(c, hbm_set_tstep(c->hbm, tstep, gf, gb, G.glo, G.gsz, G.goff, G.gtotal));
   }
   return upload_gates(c);
+}
+
+int ocg_set_potential(ocg_ctx* c, const double* eps) {
+  if (!c) return OCG_EINVAL;
+  const int L = c->P.L;
+  bool any = false;
+  for (int k = 0; eps && k < L; ++k) {
+    if (!std::isfinite(eps[k])) return fail(c, OCG_EINVAL, "site energies must be finite");
+    any = any || eps[k] != 0.0;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->have_psi = c->have_xi = c->have_xih = false;
+  c->u_psi.clear();  // trajectories of the old potential are never reused
+  c->u_xi.clear();
+  if (any) c->eps.assign(eps, eps + L);
+  else c->eps.clear();  // all zeros: the homogeneous chain, as NULL
+  if (c->hbm) return hb(c, hbm_set_potential(c->hbm, any ? eps : nullptr));
+  return upload_gates(c);
+}
+
+int ocg_get_potential(const ocg_ctx* c, double* eps) {
+  if (!c || !eps) return OCG_EINVAL;
+  for (int k = 0; k < c->P.L; ++k) eps[k] = c->eps.empty() ? 0.0 : c->eps[size_t(k)];
+  return 0;
 }
 
 static int launch_steps(ocg_ctx* c, int slot, const double* u, int nsteps, int forward) {

@@ -81,6 +81,23 @@ inline void gate_tables(OcgParams& P, double J, std::vector<double>& gf, std::ve
   P.gtotal = off;
 }
 
+// Half-phases of the static site potential sum_k eps_k n_k for P's dt and time
+// mode: 2 L p complex (re, im), [dir][k-1][n] = exp(-i tau eps_k n / 2)
+// with tau = +dt (dir 0) or -dt (dir 1); imaginary time: the weights
+// exp(-tau eps_k n / 2).  eps is the caller's, so the arguments are unbounded: libm.
+inline std::vector<double> potential_phases(const OcgParams& P, const std::vector<double>& eps) {
+  std::vector<double> t(size_t(4) * P.L * P.p);
+  for (int dir = 0; dir < 2; ++dir)
+    for (int k = 0; k < P.L; ++k)
+      for (int n = 0; n < P.p; ++n) {
+        const double tau = dir ? -P.dt : P.dt, a = -0.5 * eps[k] * tau * n;
+        const size_t o = 2 * ((size_t(dir) * P.L + k) * P.p + n);
+        t[o] = P.imag ? std::exp(a) : std::cos(a);
+        t[o + 1] = P.imag ? 0.0 : std::sin(a);
+      }
+  return t;
+}
+
 // Per-sector Schmidt-rank bounds for the HBM engine (no LDS capacity
 // limits): md[b][q] = min(HS_left, HS_right), mdz[b][q] = min(HS_left,
 // 2 min(HS_left, HS_right)) (inside the dH zip-up), clamped to 2^30.

@@ -27,12 +27,15 @@ def sector_basis(L: int, p: int, N: int):
     return confs, {c: i for i, c in enumerate(confs)}
 
 
-def bh_hamiltonian(L: int, p: int, N: int, J: float, U: float) -> np.ndarray:
+def bh_hamiltonian(L: int, p: int, N: int, J: float, U: float, eps=None) -> np.ndarray:
+    """eps: optional site energies (L,) of the static potential sum_k eps_k n_k"""
     confs, index = sector_basis(L, p, N)
     D = len(confs)
     H = np.zeros((D, D))
     for col, c in enumerate(confs):
         H[col, col] += 0.5 * U * sum(n * (n - 1) for n in c)
+        if eps is not None:
+            H[col, col] += sum(float(e) * n for e, n in zip(eps, c))
         for i in range(L - 1):
             n1, n2 = c[i], c[i + 1]
             # a_i a^dag_{i+1}
@@ -46,10 +49,10 @@ def bh_hamiltonian(L: int, p: int, N: int, J: float, U: float) -> np.ndarray:
     return H
 
 
-def ground_state_full(L: int, p: int, N: int, J: float, U: float):
+def ground_state_full(L: int, p: int, N: int, J: float, U: float, eps=None):
     """Ground state as a dense p**L vector (site 1 most significant)."""
     confs, _ = sector_basis(L, p, N)
-    H = bh_hamiltonian(L, p, N, J, U)
+    H = bh_hamiltonian(L, p, N, J, U, eps)
     w, v = np.linalg.eigh(H)
     g = v[:, 0]
     g = g * np.sign(g[np.argmax(np.abs(g))])
@@ -215,23 +218,31 @@ def gate_list(L: int):
 
 
 def exact_step(psi: np.ndarray, L: int, p: int, J: float, dt: float, u_from: float, u_to: float,
-               forward: bool = True) -> np.ndarray:
-    """Untruncated version of BH_tDMRG::step (same gate order, same U split)."""
+               forward: bool = True, eps=None) -> np.ndarray:
+    """Untruncated version of BH_tDMRG::step (same gate order, same U split).  eps: site energies (L,) of
+    the static potential; its half-phase exp(-i tau eps_k n / 2) joins each U half-phase of site k."""
     tau = dt if forward else -dt
     n = np.arange(p)
     ph_f = np.exp(-1j * 0.25 * u_from * tau * n * (n - 1))
     ph_t = np.exp(-1j * 0.25 * u_to * tau * n * (n - 1))
+    if eps is not None:
+        eps = np.asarray(eps, float).reshape(L)
+        ph_f = ph_f[None, :] * np.exp(-1j * 0.5 * tau * eps[:, None] * n[None, :])
+        ph_t = ph_t[None, :] * np.exp(-1j * 0.5 * tau * eps[:, None] * n[None, :])
+    else:
+        ph_f = np.broadcast_to(ph_f, (L, p))
+        ph_t = np.broadcast_to(ph_t, (L, p))
     G = hop_gate(p, J, tau).reshape(p, p, p, p)
     T = psi.reshape((p,) * L)
     for k in range(L):
         shape = [1] * L; shape[k] = p
-        T = T * ph_f.reshape(shape)
+        T = T * ph_f[k].reshape(shape)
     for (i1, i2) in gate_list(L):
         T = np.tensordot(G, T, axes=([2, 3], [i1 - 1, i2 - 1]))
         T = np.moveaxis(T, [0, 1], [i1 - 1, i2 - 1])
     for k in range(L):
         shape = [1] * L; shape[k] = p
-        T = T * ph_t.reshape(shape)
+        T = T * ph_t[k].reshape(shape)
     out = T.reshape(-1)
     return out / np.linalg.norm(out)
 

@@ -7,6 +7,9 @@
 //   setTstep / getTstep / getArgs            (:35, :38, :39)
 //   step(psi, from, to, propagateForward)    (:36; src/BH_tDMRG.cpp:111-230)
 //   propagatorDeriv(u)                       (:37; src/BH_tDMRG.cpp:238-241)
+// Beyond the reference: setPotential(eps) / getPotential(), the static site
+// potential sum_k eps_k n_k of every step (ocg_set_potential); propagatorDeriv
+// is unchanged by it.
 // The particle number is taken from the states (ITensor infers it from the
 // IQMPS quantum numbers), so device contexts are created on first use.
 //
@@ -83,6 +86,20 @@ class GpuTDMRG {
     scratch = std::make_shared<Scratch>();  // contexts carry dt-dependent gates
   }
   double getTstep() const { return tstep; }
+  // static site potential sum_k eps_k n_k (L site energies, site 1 first; empty or all zeros: none).
+  // Every context created afterwards carries it: single steps, and the shards of an
+  // OptimalControl constructed from this stepper afterwards (like setTstep).
+  void setPotential(std::vector<double> e) {
+    if (!e.empty() && e.size() != size_t(L)) throw std::invalid_argument("setPotential: eps must have L entries");
+    eps = std::move(e);
+    scratch = std::make_shared<Scratch>();
+  }
+  std::vector<double> getPotential() const { return eps.empty() ? std::vector<double>(size_t(L), 0.0) : eps; }
+  bool hasPotential() const {
+    for (double e : eps)
+      if (e != 0.0) return true;
+    return false;
+  }
   Args getArgs() const { return args; }
   DerivMPO propagatorDeriv(const double& /*control_n*/) const {
     DerivMPO m{L, p, std::vector<double>(p)};
@@ -122,12 +139,19 @@ class GpuTDMRG {
     std::mutex mu;
     std::map<int, detail::CtxPtr> byQ;
   };
+  // a context of this stepper's chain on device dev with its site potential set
+  detail::CtxPtr new_ctx(int dev, int Q) const {
+    detail::CtxPtr c = detail::make_ctx(dev, L, p, Q, J, tstep, args);
+    if (!eps.empty()) detail::check(ocg_set_potential(c.get(), eps.data()), c.get(), "ocg_set_potential");
+    return c;
+  }
   ocg_ctx* scratch_ctx(int Q) const {
     std::lock_guard<std::mutex> lk(scratch->mu);
     auto& c = scratch->byQ[Q];
-    if (!c) c = detail::make_ctx(device, L, p, Q, J, tstep, args);
+    if (!c) c = new_ctx(device, Q);
     return c.get();
   }
+  std::vector<double> eps;
   int L = 0, p = 0, device = 0;
   double J = 1.0, tstep = 0.01;
   Args args;
@@ -158,7 +182,7 @@ class GpuTDMRG::Engine {
       // shard s on device (first + s) mod #devices: more shards than GPUs run
       // concurrently on separate streams of the same device
       const int dev = (stepper.device + int(shards.size())) % ndev;
-      detail::CtxPtr c = detail::make_ctx(dev, stepper.L, stepper.p, tgt.Q, stepper.J, stepper.tstep, stepper.args);
+      detail::CtxPtr c = stepper.new_ctx(dev, tgt.Q);  // (with the stepper's site potential)
       detail::check(ocg_set_states(c.get(), tgt.dims.data(), tgt.raw(), ini.dims.data(), ini.raw()), c.get(),
                     "ocg_set_states");
       shards.push_back(std::move(c));
@@ -427,6 +451,8 @@ class GpuTDMRG::Engine {
   int sites() const { return stepper.L; }
   int levels() const { return stepper.p; }
   int particles() const { return tgt.Q; }
+  // a non-zero site potential is in force on every shard
+  bool hasPotential() const { return stepper.hasPotential(); }
   // launches of one ocg_kernel_stats kind on shard 0 since the context was created (diagnostics: kind 0
   // counts the trajectory propagations)
   long kernelLaunches(int kind) {

@@ -16,6 +16,11 @@
 //   certificate     optional out-parameters: the energy <H(J, U)> of the returned
 //                   state, its variance <H^2> - <H>^2 (0 for an eigenstate) and the
 //                   seven raw moments behind them (ocg_observe_moments_states)
+//   site potential  the overload with site energies eps adds sum_k eps_k n_k to H
+//                   (ocg_set_potential).  Its energy / variance out-parameters
+//                   throw std::invalid_argument when eps is not zero: they describe
+//                   the homogeneous H, and the variance with a potential needs
+//                   <K V> and <D V>, which ocg_observe_moments does not return
 #pragma once
 
 #include <cmath>
@@ -52,14 +57,24 @@ inline void check(int rc, const ocg_ctx* c, const char* what) {
 }
 }  // namespace detail_gs
 
+// the ground state in the static site potential sum_k eps_k n_k (eps: L site energies, site 1 first)
 inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const double J, const double U,
-                           const int maxBondDim, const double threshold, bool /*silent*/ = true, int device = 0,
-                           double* energy = nullptr, double* variance = nullptr, double* moments7 = nullptr) {
+                           const std::vector<double>& eps, const int maxBondDim = 200, const double threshold = 1e-9,
+                           bool /*silent*/ = true, int device = 0, double* energy = nullptr,
+                           double* variance = nullptr, double* moments7 = nullptr) {
   const int L = sites.N(), p = sites.localDim();
+  if (!eps.empty() && eps.size() != size_t(L)) throw std::invalid_argument("InitializeState: eps must have L entries");
+  bool trapped = false;
+  for (double e : eps) trapped = trapped || e != 0.0;
+  if (trapped && (energy || variance))
+    throw std::invalid_argument(
+        "InitializeState: the energy and variance out-parameters describe the homogeneous Hamiltonian; with a "
+        "site potential they need <K V> and <D V>, which ocg_observe_moments does not return");
   MPS psi = productState(L, p, Npart);
   ocg_ctx* c = nullptr;
   detail_gs::check(ocg_create(device, L, p, Npart, J, 0.01, threshold, maxBondDim, &c), nullptr, "ocg_create");
   try {
+    if (trapped) detail_gs::check(ocg_set_potential(c, eps.data()), c, "ocg_set_potential");
     ocg_info info;
     detail_gs::check(ocg_get_info(c, &info), c, "ocg_get_info");
     std::vector<int> od(psi.dims.size());
@@ -96,6 +111,13 @@ inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const doub
   }
   ocg_destroy(c);
   return psi;
+}
+
+inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const double J, const double U,
+                           const int maxBondDim, const double threshold, bool silent = true, int device = 0,
+                           double* energy = nullptr, double* variance = nullptr, double* moments7 = nullptr) {
+  return InitializeState(sites, Npart, J, U, std::vector<double>(), maxBondDim, threshold, silent, device, energy,
+                         variance, moments7);
 }
 
 inline MPS InitializeState(const BoseHubbard& sites, const int Npart, const double J, const double U,

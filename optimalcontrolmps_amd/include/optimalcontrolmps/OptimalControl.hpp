@@ -149,10 +149,16 @@ class OptimalControl {
   // converted) and the stepper's J: the drift of E over stretches of constant u measures
   // Trotter plus truncation error, E_T - E_0(u_T) is the residual energy of a ramp.  Reads the
   // device trajectory (Engine::observeMoments); nothing is propagated.  Only for steppers
-  // whose Engine has observeMoments() and that have hopping() (GpuTDMRG).
+  // whose Engine has observeMoments() and that have hopping() (GpuTDMRG).  H here is the
+  // homogeneous chain's: with a non-zero site potential on the stepper this throws
+  // std::invalid_argument (the variance would need <K V> and <D V>, which the moments lack).
   ocmps::TrajectoryEnergies getPsitEnergies(const stdvec& control) {
     const stdvec u = GRAPE ? control : basis.convertControl(control);
     if (u.size() != N) throw std::invalid_argument("getPsitEnergies: control has the wrong length");
+    if (engine->hasPotential())
+      throw std::invalid_argument(
+          "getPsitEnergies: the energies describe the homogeneous Hamiltonian; with a site potential the energy "
+          "and its variance need <K V> and <D V>, which ocg_observe_moments does not return");
     ocmps::TrajectoryEnergies r;
     r.moments = engine->observeMoments(0, {});
     const double J = timeStepper.hopping();

@@ -108,6 +108,8 @@ SIGNATURES = [
     ("ocg_abi_version", C.c_int, []),
     ("ocg_get_path_stats", C.c_int, [C.c_void_p, C.POINTER(OcgPathStats)]),
     ("ocg_set_tstep", C.c_int, [C.c_void_p, C.c_double]),
+    ("ocg_set_potential", C.c_int, [C.c_void_p, dp]),
+    ("ocg_get_potential", C.c_int, [C.c_void_p, dp]),
     ("ocg_mps_nelem", C.c_size_t, [C.c_int, C.c_int, C.c_int, ip]),
     ("ocg_step", C.c_int, [C.c_void_p, ip, dp, C.c_double, C.c_double, C.c_int, ip, dp, C.c_size_t, szp]),
     ("ocg_steps", C.c_int, [C.c_void_p, ip, dp, dp, C.c_int, C.c_int, ip, dp, C.c_size_t, szp]),
@@ -270,6 +272,27 @@ class Engine:
 
     def _wrap(self, fd, d, n):
         return MPS(self.L, self.p, self.Q, fd.copy(), d[:2 * n.value].view(np.complex128).copy())
+
+    # ------------------------------------------------ static site potential
+    def set_potential(self, eps=None):
+        """Site energies eps[L] of the static potential sum_k eps_k n_k (trap, tilt, disorder) of every later
+        step, real and imaginary time; None (or all zeros) clears it.  Drops the device trajectories."""
+        if eps is None:
+            self._chk(lib().ocg_set_potential(self.h, None), "ocg_set_potential")
+        else:
+            e = np.asarray(eps, np.float64)
+            if e.shape != (self.L,):
+                raise ValueError(f"eps must have shape ({self.L},)")
+            e, pe = _d(e)
+            self._chk(lib().ocg_set_potential(self.h, pe), "ocg_set_potential")
+        lib().ocg_get_info(self.h, C.byref(self.info))
+
+    @property
+    def potential(self):
+        """the site energies in force (zeros when none is set)"""
+        e = np.zeros(self.L)
+        self._chk(lib().ocg_get_potential(self.h, e.ctypes.data_as(dp)), "ocg_get_potential")
+        return e
 
     # ------------------------------------------------ TimeStepper-level
     def step(self, m: MPS, u_from, u_to, forward=True) -> MPS:

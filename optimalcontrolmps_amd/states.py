@@ -51,12 +51,21 @@ GS_TAUS = (0.05, 0.01, 0.002, 0.001, 0.0005)
 
 
 def ground_state(engine, U: float, taus=GS_TAUS, block: int = 25, tol: float = 1e-13,
-                 max_steps: int = 8000, psi: MPS = None) -> MPS:
+                 max_steps: int = 8000, psi: MPS = None, eps=None) -> MPS:
     """InitializeState(sites, Npart, J, U) (include/InitializeState.hpp:18-117) on
     the device: imaginary-time evolution exp(-tau H) of the product state
     |0..0 1..1> (the reference's DMRG starting guess), per tau in blocks of
     `block` steps until 1 - |<prev|new>| < tol, the whole schedule in one
-    ocg_ground_state call (the state stays on the device)."""
+    ocg_ground_state call (the state stays on the device).  eps: site energies of a static potential
+    sum_k eps_k n_k for this call (Engine.set_potential; the engine's own potential is put back afterwards,
+    and its device trajectories are dropped); None: whatever potential the engine has."""
     if psi is None:
         psi = product_state(engine.L, engine.p, engine.Q)
-    return engine.ground_state(psi, U, taus, block, tol, max_steps)[0]
+    if eps is None:
+        return engine.ground_state(psi, U, taus, block, tol, max_steps)[0]
+    old = engine.potential
+    engine.set_potential(eps)
+    try:
+        return engine.ground_state(psi, U, taus, block, tol, max_steps)[0]
+    finally:
+        engine.set_potential(old)
